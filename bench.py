@@ -6,7 +6,9 @@ HBM-resident compressed corpus.  Default workload = BASELINE.json configs[1]:
 1M docs x 128 tok x dim128 (nbits 4, 2^17 centroids), batch 64 queries x 32 tok, top_k=1000,
 n_full_scores=4096 (R=1024 exact-scored docs / query), n_ivf_probe=8.
 
-    python bench.py                               # N=1, finishes in a few minutes
+    python bench.py                               # N=1: set-up, warm-up, the timed steps, the result line (seconds)
+    python bench.py --full                        # + everything else this file measures (below); a few minutes
+    python bench.py --dump-outputs DIR            # + DIR/{pids,scores,counts}.npy: what the last timed step returned
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N         # N GPUs, one process each (RCCL)
 
@@ -20,9 +22,13 @@ GPU, one process per GPU -- with every rank searching its OWN batch per step thr
 With --alt-mode a second mode is timed too and reported as `alt_mode`.
 
 One JSON line on rank 0.  `value` is timed on the boundary call fp_search (host query buffer in, host
-results out -- what the reference's pysearch hands over, rust/lib.rs:195-223); the same steps with queries and
-results resident in HBM (fp_search_device) are reported as `value_device_io`.  Every step uses its own query
-batch.  `roofline` describes the DOMINANT kernel of the step: whichever of the three single-kernel stages -- S1's centroid
+results out -- what the reference's pysearch hands over, rust/lib.rs:195-223).  Every step uses its own query
+batch; corpus and queries are seeded, so the same arguments give the same inputs in every run and on every build.
+A plain run stops there.  With --full the runs that take passes of their own follow the timed region: the same steps
+with queries and results resident in HBM (fp_search_device) are reported as `value_device_io`, the timed region five
+more times as `repeat_ms_per_step`, the per-stage pass with graph replay off as `stages_ms` and the `roofline`
+objects, the plain-C oracle on the host as `cpu_baseline` / `parity_vs_cpu`.
+`roofline` describes the DOMINANT kernel of the step: whichever of the three single-kernel stages -- S1's centroid
 GEMM (MFMA bound), S4's per-candidate scan (HBM), the fused decompress + MaxSim kernel (HBM; the kernel BASELINE.json's north star
 puts the roofline target on) -- has the longest measured launch; all three are always under `roofline_by_kernel` (the MaxSim entry
 also with its exact-order repair included: `frac_with_repair`); `stages_ms` gives every stage.
@@ -64,7 +70,14 @@ def parse():
     ap.add_argument("--nprobe", type=int, default=8)
     ap.add_argument("--dim", type=int, default=128)
     ap.add_argument("--nbits", type=int, default=4)
-    ap.add_argument("--cpu-queries", type=int, default=-1, help="queries for the CPU baseline leg (0 = skip, -1 = auto)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need, each in passes of its own after the timed region: the repeats of "
+                         "the timed region, the per-stage pass (stages_ms, roofline), fp_search_device (value_device_io), the CPU baseline "
+                         "and its parity check")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps, write what the last of them returned as DIR/pids.npy, DIR/counts.npy (float64) and "
+                         "DIR/scores.npy (float32)")
+    ap.add_argument("--cpu-queries", type=int, default=-1, help="--full: queries for the CPU baseline leg (0 = skip, -1 = auto)")
     ap.add_argument("--workload", type=str, default="", help="label override")
     ap.add_argument("--dup-centroids", type=int, default=0, help="make centroid rows 1000 .. 1000 + N identical (exact ties of the centroid scores: a query "
                     "token near them overflows the threshold probe's tie room and takes its fallback); 0 = the config's table")
@@ -87,6 +100,8 @@ def parse():
                     help="gloo = result gather through CPU tensors, ranks wrapped onto the visible GPUs (testing the multi-process "
                          "path on a box with fewer GPUs than ranks)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     a.cfg = a.config if a.config != "auto" else ("cfg3" if max(world, a.gpus) > 1 else "cfg2")
     if a.docs == 0:
@@ -124,6 +139,16 @@ def _pmc_traffic(kernel_prefix, applicable):
         if name.startswith(kernel_prefix) and "hbm_read_bytes_corrected" in e:
             return int(e["hbm_read_bytes_corrected"]), "profiles/" + os.path.basename(files[-1])
     return None, None
+
+
+def _dump_outputs(path, result):
+    """the (pids, scores, counts) of one step as the caller received them: ids and counts exactly in float64, scores in float32
+    (3 x batch x top_k numbers at most: ~1 MB at the defaults, 5 MB for cfg3's batch of 256)"""
+    os.makedirs(path, exist_ok=True)
+    for name, x, dt in zip(("pids", "scores", "counts"), result, (np.float64, np.float32, np.float64)):
+        if hasattr(x, "detach"):   # (the torch transport of the sharded modes hands tensors over)
+            x = x.detach().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(np.asarray(x), dtype=dt))
 
 
 def main():
@@ -244,16 +269,20 @@ def main():
         repaired_total = 0
         sync()
         t_start = time.perf_counter()
+        last = None
         for i in range(a.steps):
             ts = time.perf_counter()
-            step(a.warmup + i)
+            last = step(a.warmup + i)
             lat.append(time.perf_counter() - ts)
         sync()
         elapsed = time.perf_counter() - t_start
+        if a.dump_outputs and mode == primary and rank == 0:
+            _dump_outputs(a.dump_outputs, last)
+        del last
         # `value` is the K steps above and nothing else.  K = 20 steps are ~37 ms: for the reader, the same K steps five more times
         # (reported as `repeat_ms_per_step`: how far one timed region of this length scatters on this box)
         repeats = []
-        if mode == "single":
+        if mode == "single" and a.full:
             for _ in range(5):
                 sync()
                 t_r = time.perf_counter()
@@ -261,7 +290,7 @@ def main():
                     step(a.warmup + i)
                 sync()
                 repeats.append((time.perf_counter() - t_r) / a.steps * 1e3)
-        if mode in ("single", "replica"):
+        if mode in ("single", "replica") and a.full:
             # per-stage HIP-event times and work counters: the SAME K steps once more with graph replay off -- in the timed loop
             # above every step is one hipGraphLaunch, which records no per-stage events (same kernels, same launch parameters)
             was = R.set_graph_replay(False)
@@ -284,7 +313,7 @@ def main():
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             elapsed = float(tt.item())
         dev_elapsed = None
-        if mode == "single":   # the same K steps with queries uploaded beforehand and results left in HBM
+        if mode == "single" and a.full:   # the same K steps with queries uploaded beforehand and results left in HBM
             devid = index.device_id
             dq = [R.DeviceBuffer(devid, q.nbytes).upload(q) for q in batches]
             dp = R.DeviceBuffer(devid, a.batch * max(a.topk, 1) * 8)
@@ -357,8 +386,9 @@ def main():
             "index_bytes_per_gpu": index_bytes, "index_build_s": round(t_build, 2),
         },
         "p50_ms": float(np.percentile(np.array(lat) * 1e3, 50)), "p90_ms": float(np.percentile(np.array(lat) * 1e3, 90)),
-        "repeat_ms_per_step": [round(x, 4) for x in res.get("repeats", [])],
     }
+    if a.full:
+        out["repeat_ms_per_step"] = [round(x, 4) for x in res.get("repeats", [])]
     if primary in ("shard", "split", "grid") or (a.cfg == "cfg3" and world == 1):
         # the one-GPU anchor of the strong-scaling series: `python bench.py --gpus 1 --config cfg3` (the newest committed measurement of it)
         import glob
@@ -377,7 +407,7 @@ def main():
             a.batch * a.qlen * a.dim * 2 // 1024, a.batch * a.topk * 12 // 1024)
         out["value_device_io"] = {"value": a.batch * a.steps / dev_elapsed, "ms_per_step": dev_elapsed / a.steps * 1e3,
                                   "note": "fp_search_device: queries uploaded before the timed region, results left in HBM"}
-    if primary in ("single", "replica") and rank == 0:   # (replica: rank 0's own kernels; every rank runs the same pipeline)
+    if a.full and primary in ("single", "replica") and rank == 0:   # (replica: rank 0's own kernels; every rank runs the same pipeline)
         stages = {k: v / a.steps for k, v in stage_acc.items()}
         out["stages_ms"] = {k: round(v, 4) for k, v in stages.items()}
         out["stages_note"] = ("HIP-event stage times of the same K steps repeated with graph replay off (in the timed loop a step is "
@@ -480,6 +510,13 @@ def main():
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import plaid_oracle as OC
             cores = OC.num_procs()
+            # the cores this process may use, where that is fewer than the host's: its affinity mask, and OMP_NUM_THREADS where the
+            # environment sets one (a quota does not show in either count, and 256 threads on 16 cores take 16 x as long)
+            if hasattr(os, "sched_getaffinity"):
+                cores = min(cores, len(os.sched_getaffinity(0)))
+            omp = os.environ.get("OMP_NUM_THREADS", "").split(",")[0].strip()
+            if omp.isdigit() and int(omp) > 0:
+                cores = min(cores, int(omp))
             if ncpu < 0:   # one query per host core (OpenMP over queries, dynamic schedule), at least one batch
                 ncpu = min(max(a.batch, cores), a.batch * n_batches, 512)
             arr = R.export_index_arrays(index, centroids=cent, bucket_weights=bw)

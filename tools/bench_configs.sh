@@ -3,7 +3,7 @@
 # (warm-up 4: a shape's plain call, its learnt-capacity call and the capturing call (+ anything the runtime initialises at a process's first graph:
 # profiles/r06_first_graph_cost.txt) lie before the timed region; until r06_c the warm-up was 2)
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out; mkdir -p $OUT
-run() { name=$1; shift; timeout 300 python $R/bench.py --steps 5 --warmup 4 --cpu-queries 0 --workload "$name" "$@" 2>$OUT/cfg_$name.err | python -c "
+run() { name=$1; shift; timeout 300 python $R/bench.py --full --steps 5 --warmup 4 --cpu-queries 0 --workload "$name" "$@" 2>$OUT/cfg_$name.err | python -c "
 import sys,json
 d=json.loads(sys.stdin.read())
 allk=[d['roofline']]+list(d['roofline_by_kernel'].values())

@@ -8,7 +8,7 @@ cd $R
 cp fast-plaid_amd/libfastplaid_hip.so /tmp/lib_orig.so
 for f in /tmp/lib_orig.so tools/libs/lib_msabl*.so; do
   cp $f fast-plaid_amd/libfastplaid_hip.so
-  timeout 200 python bench.py --steps 10 --warmup 3 --cpu-queries 0 2>/dev/null | python -c "
+  timeout 200 python bench.py --full --steps 10 --warmup 3 --cpu-queries 0 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read()); print('$(basename $f)', 'maxsim_ms=%.4f repair_ms=%.4f step_ms=%.3f' % (d['stages_ms']['S6+S7 maxsim'], d['stages_ms']['S7 order repair'], d['ms_per_step']))" | tee -a $OUT/r3_msabl.txt
 done

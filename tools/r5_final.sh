@@ -7,7 +7,7 @@ bash tools/profile_round.sh $T > $OUT/${T}_profile_round.log 2>&1
 tail -4 $OUT/${T}_profile_round.log | cut -c1-600
 cd $R
 for B in 1 8; do
-  timeout 200 python bench.py --batch $B --steps 60 --warmup 10 --cpu-queries 0 2>/dev/null | python -c "
+  timeout 200 python bench.py --full --batch $B --steps 60 --warmup 10 --cpu-queries 0 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('B=$B: mean %.4f ms  p50 %.4f ms  p90 %.4f ms (fp_search through the replayed graph, 60 steps)' % (d['ms_per_step'], d['p50_ms'], d['p90_ms']))"

@@ -3,7 +3,7 @@
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out; cd $R; mkdir -p $OUT
 for v in "" "$@"; do
   if [ -n "$v" ]; then export FP_LIB_PATH=$R/$v; else unset FP_LIB_PATH; fi
-  timeout 300 python bench.py --cpu-queries 0 --steps 30 --warmup 5 > $OUT/knob.json 2> $OUT/knob.err
+  timeout 300 python bench.py --full --cpu-queries 0 --steps 30 --warmup 5 > $OUT/knob.json 2> $OUT/knob.err
   python - "$v" <<PY
 import json, sys
 d = json.load(open("$OUT/knob.json"))

@@ -5,7 +5,7 @@ TAG=${1:-r5mic}
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out; cd $R; mkdir -p $OUT
 LAZY_EXPECT=1 timeout 600 python tests/lazy_worker.py 2>&1 | tail -2
 timeout 900 python -m pytest tests/test_zz_graph_replay.py tests/test_hip_parity.py -m gpu -x -q -k "graph or lazy or probe or golden or synthetic_vs_oracle or randomized or level0 or subset or spec or n_full or ties" 2>&1 | tail -3
-timeout 300 python bench.py --cpu-queries 0 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+timeout 300 python bench.py --full --cpu-queries 0 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 python - <<PY
 import json
 d = json.load(open("$OUT/${TAG}_bench.json"))

@@ -3,7 +3,7 @@
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out; cd $R; mkdir -p $OUT
 run() { lib="$1"; knob="$2"; shift 2
   if [ -n "$lib" ]; then export FP_LIB_PATH=$R/$lib; else unset FP_LIB_PATH; fi
-  FP_TEST="$knob" timeout 400 python bench.py --cpu-queries 0 --steps 6 --warmup 3 "$@" > $OUT/knob.json 2> $OUT/knob.err
+  FP_TEST="$knob" timeout 400 python bench.py --full --cpu-queries 0 --steps 6 --warmup 3 "$@" > $OUT/knob.json 2> $OUT/knob.err
   python - "$lib" "$knob" "$*" <<PY
 import json, sys
 d = json.load(open("$OUT/knob.json"))

@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out; cd $R; mkdir -p $OUT
 timeout 1200 python -m pytest tests/test_hip_parity.py -m gpu -x -q -k "level0 or lazy or full_size_properties" 2>&1 | tail -4
 for e in "X=0" "FP_TEST=l0_rsh=17"; do
   echo "== $e"
-  env $e timeout 900 python bench.py --gpus 1 --config cfg3 --steps 5 --warmup 2 --cpu-queries 0 2>/dev/null | python -c "
+  env $e timeout 900 python bench.py --full --gpus 1 --config cfg3 --steps 5 --warmup 2 --cpu-queries 0 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read())
 k=[v for v in [d['roofline']]+list(d['roofline_by_kernel'].values()) if 'candidate_docs_per_batch' in v][0]

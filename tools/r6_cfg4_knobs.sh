@@ -4,7 +4,7 @@ TAG=${1:-r6cfg4k}; shift
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out; cd $R; mkdir -p $OUT
 for e in "$@"; do
   echo "== $e"
-  env $e timeout 300 python $R/bench.py --steps 10 --warmup 3 --cpu-queries 0 --workload cfg4 --docs 100000 --doc-len 1024 --batch 32 --topk 100 2>/dev/null | python -c "
+  env $e timeout 300 python $R/bench.py --full --steps 10 --warmup 3 --cpu-queries 0 --workload cfg4 --docs 100000 --doc-len 1024 --batch 32 --topk 100 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read())
 k=[v for v in [d['roofline']]+list(d['roofline_by_kernel'].values()) if 'candidate_docs_per_batch' in v][0]

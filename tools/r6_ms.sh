@@ -19,7 +19,7 @@ PY
 }
 for lib in "" "$@" "" "$@"; do
   echo "== ${lib:-tree}"
-  FP_LIB_PATH=${lib:+$R/$lib} timeout 300 python bench.py --cpu-queries 16 --steps 40 --warmup 8 2>/dev/null | python -c "
+  FP_LIB_PATH=${lib:+$R/$lib} timeout 300 python bench.py --full --cpu-queries 16 --steps 40 --warmup 8 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read()); print('  ', round(d['ms_per_step'],4), 'p50', round(d.get('p50_ms',0),4), 'dev', round(d['value_device_io']['ms_per_step'],4), d.get('parity_vs_cpu'), {k:round(v,4) for k,v in d['stages_ms'].items() if 'maxsim' in k or 'repair' in k})"
   kt ${lib:+$R/$lib}
