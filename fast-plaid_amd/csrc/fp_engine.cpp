@@ -963,7 +963,8 @@ static int run_front(Pipe& P, const int64_t* h_sub_ids, const int64_t* h_sub_off
   const bool s1x_stats = s1_stats_enabled() && !s->capturing;
   P.s1_mode = P.lazy ? 3 : (s1x_env <= 0 ? 0 : (s1x_env == 2 ? 2 : 1));   // (FP_S1_EXACT=3, the default: lazy where it applies, eager elsewhere)
   const float dim_scale = D.dim > 128 ? (float)D.dim / 128.0f : 1.0f;
-  FpS1Exact xe{P.s1_mode, nullptr, s1x_kappa * dim_scale, nullptr};
+  static const int s1_direct = fp_test_opt("s1_direct", 1) != 0 ? 1 : 0;   // the streaming kernel's direct write-out (0: the staged one everywhere, for A/B runs)
+  FpS1Exact xe{P.s1_mode, nullptr, s1x_kappa * dim_scale, nullptr, s1_direct};
   if (P.s1_mode) {
     HIPCHK(s->wcol.ensure((size_t)B * sh.Qp * 4 + 16));
     xe.wcol = s->wcol.as<float>();

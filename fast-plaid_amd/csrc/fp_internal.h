@@ -181,6 +181,8 @@ struct FpS1Exact {
   float kappa;                 // relative part of the window
   unsigned long long* stats;   // nullable [4]: flagged entries, repaired values that differ from the MFMA's, entries beyond the
                                // LDS list (slow path), mode 2: unflagged differences
+  int direct;                  // streaming kernel: S leaves straight from the MFMA accumulators where the launch allows it (modes 0 / 3,
+                               // Qp == 32, no 8-bit bins); 0: the LDS-staged write-out everywhere (FP_TEST=s1_direct=0, A/B runs)
 };
 // S1's LAZY form (round 5; FpS1Exact::mode 3): S1 stores the upper candidate h(x + u) of EVERY score and runs no chain at all; a
 // stored value is the reference's or (rarely) one fp16 step above it.  The consumers settle only what they use:

@@ -580,10 +580,64 @@ __global__ __launch_bounds__(128 * NWC) void k_centroid_scores(const uint16_t* _
 // after an LDS-writing load it knows of with vmcnt(0), which would serialise the prefetch with the MFMA phase; here the one wait
 // sits in the epilogue in front of the tile's stores and the barrier at the top of the loop publishes the buffer.
 // (One-tile-per-workgroup form above: 64 KB of operands per tile in two serialised round trips, 201 us without its write-out.)
+// DIRECT (round 7; plain or lazy S, Qp == 32, no 8-bit bins -- the launcher decides): no staging at all.  The A fragments are
+// loaded with the query columns relabelled so that a lane's accumulators are 16 consecutive columns of one centroid's row; S, the
+// excess byte and the column maxima leave straight from the registers, and the tile loop's top barrier is the only one left
+// (cfg2: 223 -> 183 us, profiles/r07_s1_store.txt).  The eager modes, Qp 64 / 128 and the 8-bit bins keep the staged epilogue.
 // one of the two LDS buffers: the operand tile (128 rows of DK halves; the staged output tile and, behind it at 32 KiB, the epilogue's
 // column-maximum scratch reuse the space) -- 33 KiB up to dim 128, 65 KiB at dim 256 (one workgroup per CU then)
 static constexpr int s1_buf_bytes(int dk) { return (128 * dk * 2 > 4 * 128 * 64 ? 128 * dk * 2 : 4 * 128 * 64) + 4 * 128 * 2; }
-template <int DK>
+// ---- the DIRECT write-out (round 7; modes 0 / 3, Qp == 32, no 8-bit bins): S leaves straight from the MFMA accumulators ---------
+// The 32x32 MFMA leaves lane (c = lane & 31, hi = lane >> 5) with the rows rho = (r & 3) + 8 (r >> 2) + 4 hi of centroid column c.
+// Which QUERY column an MFMA row is is the A operand's business: the lane that supplies row rho loads query column
+// s1_direct_qcol(rho), and element r of lane (c, hi) is then S[c][16 hi + r] -- the lane's eight packed registers are 32 contiguous
+// bytes of centroid c's row: two 16-byte stores, S in its normal order, no LDS staging, no barrier, no lane exchange.
+__device__ __forceinline__ int s1_direct_qcol(int rho) { return 16 * ((rho >> 2) & 1) + 4 * (rho >> 3) + (rho & 3); }
+// level-0 excess of one centroid over a lane's 16 columns (w: the packed scores, g: the columns' gfl words), + L0_EINF per clamped
+// bin: s1_writeout's two forms over eight registers instead of four.
+__device__ __forceinline__ uint32_t s1_direct_excess(const uint32_t (&w)[8], const uint32_t (&g)[8], const int rd) {
+  if (rd) {
+    // (the one-fma form, see s1_writeout.  The rounding-mode window is ONE asm block: nothing else can be scheduled into it.
+    // Eight biased terms per half: the sum starts at -8 * 0x6400 = 0xE000 mod 2^16; eight excesses of at most 255 fit.)
+    uint32_t y[8];
+    asm volatile(
+        "s_setreg_imm32_b32 hwreg(HW_REG_MODE, 2, 2), 2\n\ts_nop 1\n\t"
+        "v_pk_fma_f16 %0, %8, %24, %16\n\t"
+        "v_pk_fma_f16 %1, %9, %24, %17\n\t"
+        "v_pk_fma_f16 %2, %10, %24, %18\n\t"
+        "v_pk_fma_f16 %3, %11, %24, %19\n\t"
+        "v_pk_fma_f16 %4, %12, %24, %20\n\t"
+        "v_pk_fma_f16 %5, %13, %24, %21\n\t"
+        "v_pk_fma_f16 %6, %14, %24, %22\n\t"
+        "v_pk_fma_f16 %7, %15, %24, %23\n\t"
+        "s_setreg_imm32_b32 hwreg(HW_REG_MODE, 2, 2), 0\n\ts_nop 1"
+        : "=&v"(y[0]), "=&v"(y[1]), "=&v"(y[2]), "=&v"(y[3]), "=&v"(y[4]), "=&v"(y[5]), "=&v"(y[6]), "=&v"(y[7])
+        : "v"(w[0]), "v"(w[1]), "v"(w[2]), "v"(w[3]), "v"(w[4]), "v"(w[5]), "v"(w[6]), "v"(w[7]), "v"(g[0]), "v"(g[1]), "v"(g[2]),
+          "v"(g[3]), "v"(g[4]), "v"(g[5]), "v"(g[6]), "v"(g[7]), "v"(0x58005800u /*128, 128*/));
+    uint32_t acc16 = 0xE000E000u, tmax = 0x80008000u;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+      acc16 = pk_add_u16(acc16, pk_max_raw(y[t], 0x64006400u /*1024, 1024*/));
+      tmax = pk_max_i16(tmax, w[t]);
+    }
+    const uint32_t inf = ((int)(short)(tmax & 0xFFFFu) >= 0x3CD8 || (int)(short)(tmax >> 16) >= 0x3CD8) ? L0_EINF : 0u;
+    return (acc16 & 0xFFFFu) + (acc16 >> 16) + inf;
+  }
+  const h2 k128 = {(half_t)128.f, (half_t)128.f}, k155 = {(half_t)155.f, (half_t)155.f}, kzero = {(half_t)0.f, (half_t)0.f};
+  h2 dsum = kzero;
+  uint32_t tmax = 0xE400E400u;   // packed -1024
+#pragma unroll
+  for (int t = 0; t < 8; ++t) {
+    const uint32_t fl = pk_floor_raw(h2_as_u32(u32_as_h2(w[t]) * k128));
+    tmax = pk_max_raw(tmax, fl);
+    const h2 d = u32_as_h2(pk_min_raw(fl, h2_as_u32(k155))) - u32_as_h2(g[t]);
+    dsum += u32_as_h2(pk_max_raw(h2_as_u32(d), 0u));
+  }
+  // eight integer terms of at most 255 per half: each half stays below 2048, exact in fp16 (their total need not be: added as integers)
+  const h2 tm = u32_as_h2(tmax);
+  return (uint32_t)(int)(float)dsum.x + (uint32_t)(int)(float)dsum.y + ((tm.x >= (half_t)155.f || tm.y >= (half_t)155.f) ? L0_EINF : 0u);
+}
+template <int DK, bool DIRECT>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(DK > 128 ? 2 : 4, DK > 128 ? 2 : 4)))
 void k_centroid_scores_stream(const uint16_t* __restrict__ cent, const uint16_t* __restrict__ qpad, uint16_t* __restrict__ S, int64_t C,
                               int64_t Ntot, int Qp, uint8_t* __restrict__ S8, uint16_t* __restrict__ cmax, int nch, int nct, int nrt,
@@ -632,7 +686,8 @@ void k_centroid_scores_stream(const uint16_t* __restrict__ cent, const uint16_t*
   h8 af[KSTEPS];
 #pragma unroll
   for (int ks = 0; ks < KSTEPS; ++ks) {
-    const int64_t n = (int64_t)tile_n * 128 + wr * 32 + l31;
+    // (direct write-out: MFMA row l31 carries query column s1_direct_qcol(l31) of the wave's group)
+    const int64_t n = (int64_t)tile_n * 128 + wr * 32 + (DIRECT ? s1_direct_qcol(l31) : l31);
     uint4 v = make_uint4(0, 0, 0, 0);
     if (n < Ntot) v = *reinterpret_cast<const uint4*>(qpad + n * DK + (ks * 2 + hi) * 8);
     af[ks] = __builtin_bit_cast(h8, v);
@@ -645,12 +700,32 @@ void k_centroid_scores_stream(const uint16_t* __restrict__ cent, const uint16_t*
     const int64_t n = (int64_t)tile_n * 128 + tid;
     wtab[tid] = n < Ntot ? xe.wcol[n] : 0.f;
   }
+  // direct write-out: the gfl words of the 128 columns (they depend on the column only, not on the tile) take the place of the
+  // entry lists; a column group beyond the batch is never stored, so its words do not matter
+  uint16_t* gtab = reinterpret_cast<uint16_t*>(smem + 2 * S1_BUF + 512);
+  if (DIRECT && ex.e8 && tid < 128) {
+    const int64_t n = (int64_t)tile_n * 128 + tid;
+    gtab[tid] = n < Ntot ? ex.gfl[n] : (uint16_t)0;
+  }
+  // direct write-out: the column maxima of tile t wait in the tail of tile t's buffer (behind the operand tile at every dim) and
+  // leave after the NEXT barrier -- the one at the top of iteration t + 1, or the one behind the loop -- so the epilogue has none
+  auto flush_cmax = [&](int tile, uint32_t buf_off) {
+    if (cmax && tid < 128) {
+      const uint16_t* red = reinterpret_cast<const uint16_t*>(smem + buf_off + S1_BUF - 1024);
+      const int64_t n = (int64_t)tile_n * 128 + tid;
+      if (n < Ntot) {
+        const uint16_t a = red[tid], b = red[128 + tid];
+        cmax[n * nch + tile] = (mono16(b) > mono16(a)) ? b : a;
+      }
+    }
+  };
   __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): the first tile and the A fragments (a builtin: the compiler's wait insertion then knows that nothing is pending at the loop head)
   for (int t = t_first; t < t_end; ++t) {
     const uint32_t cur_off = (uint32_t)((t - t_first) & 1) * (uint32_t)S1_BUF;
     unsigned char* cur = smem + cur_off;
     __syncthreads();   // every wave's pieces of tile t have landed; nobody still reads the other buffer (tile t-1's staging)
     if (t + 1 < t_end) prefetch(t + 1, (uint32_t)S1_BUF - cur_off);
+    if (DIRECT && t > t_first) flush_cmax(t - 1, (uint32_t)S1_BUF - cur_off);
     // (the lane id is laundered per tile: every per-lane LDS address below -- the sixteen swizzled operand chunks, the staging
     // rows, the write-out offsets -- is then recomputed from it inside the iteration instead of being hoisted out of the loop,
     // where the exact mode's chains leave no registers for them and they would be spilled: a scratch reload waits with vmcnt(0),
@@ -695,9 +770,68 @@ void k_centroid_scores_stream(const uint16_t* __restrict__ cent, const uint16_t*
     uint32_t hw[1][2][8];
     uint32_t Aall = 0u;
     uint32_t A = s1_certify<1, 2>(acc, hw, xe.mode, xe.kappa, [&](int, int j) -> f2v {
-      const float2 t2 = *reinterpret_cast<const float2*>(wtab + wr * 32 + s1_col_of(2 * j, hi));
+      const float2 t2 = *reinterpret_cast<const float2*>(wtab + wr * 32 + (DIRECT ? 16 * hi + 2 * j : s1_col_of(2 * j, hi)));
       return f2v{t2.x, t2.y};
     }, &Aall);
+    if constexpr (DIRECT) {
+      // ---- direct write-out: registers hw[0][b][0..7] of lane (l31, hi) = columns 16 hi .. 16 hi + 15 of centroid wc * 64 + b * 32 + l31
+      const uint32_t bq = (uint32_t)tn * 4u + (uint32_t)wr;   // (Qp == 32: one query per 32-column group)
+      const bool gok = (int64_t)bq * 32 < Ntot;               // (uniform)
+      const int64_t cw0 = (int64_t)t * 128 + wc * 64;         // (uniform) the wave's first centroid
+      uint32_t gws[8];
+      if (ex.e8) {
+        const uint4 g0 = *reinterpret_cast<const uint4*>(gtab + wr * 32 + 16 * hi), g1 = *reinterpret_cast<const uint4*>(gtab + wr * 32 + 16 * hi + 8);
+        gws[0] = g0.x; gws[1] = g0.y; gws[2] = g0.z; gws[3] = g0.w;
+        gws[4] = g1.x; gws[5] = g1.y; gws[6] = g1.z; gws[7] = g1.w;
+      }
+      // the next tile's operand loads were issued before this tile's MFMAs: the one wait sits here, in front of the tile's stores
+      __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
+      const uint32_t lane_s = (uint32_t)(l31 * 32 + hi * 16);   // halves, within the 32-centroid block of S
+      uint32_t cm[8];
+#pragma unroll
+      for (int r = 0; r < 8; ++r) cm[r] = 0xFC00FC00u;   // packed fp16 -inf
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        const bool cok = cw0 + b * 32 + l31 < C;
+        if (gok && cok) {
+          uint16_t* Sblk = S + ((int64_t)bq * C + cw0 + b * 32) * 32;   // (uniform)
+          const uint4 v0 = make_uint4(hw[0][b][0], hw[0][b][1], hw[0][b][2], hw[0][b][3]);
+          const uint4 v1 = make_uint4(hw[0][b][4], hw[0][b][5], hw[0][b][6], hw[0][b][7]);
+          uint4* dst = reinterpret_cast<uint4*>(Sblk + lane_s);
+          dst[0] = v0;
+          dst[1] = v1;
+        }
+        if (cok) {
+#pragma unroll
+          for (int r = 0; r < 8; ++r) cm[r] = pk_max_raw(cm[r], hw[0][b][r]);
+        }
+        if (ex.e8 && gok) {   // (uniform)
+          // level 0's table entry (s1_writeout): the lane's 16 columns, then the other half's -- both halves end up with the sum
+          uint32_t acc = s1_direct_excess(hw[0][b], gws, ex.rd);
+          acc += shfl_xor_u32(acc, 32);
+          if (hi == 0 && cok) ex.e8[(int64_t)bq * ex.Cpad + cw0 + b * 32 + l31] = l0_encode(acc & (L0_EINF - 1u), acc >= L0_EINF, ex.esc + (int64_t)bq * 64);
+        }
+      }
+      if (cmax) {   // max over the wave's 64 centroids: s1_stage's DPP sequence; lane 0 of each half holds 16 columns
+        uint16_t* red = reinterpret_cast<uint16_t*>(cur + S1_BUF - 1024);
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+          uint32_t v = cm[r];
+          v = pk_max_raw(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, false));    // quad_perm [1,0,3,2]
+          v = pk_max_raw(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, false));    // quad_perm [2,3,0,1]
+          v = pk_max_raw(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x124, 0xF, 0xF, false));   // row_ror:4
+          v = pk_max_raw(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x128, 0xF, 0xF, false));   // row_ror:8
+          v = pk_max_raw(v, shfl_xor_u32(v, 16));                                                   // the other row of this half
+          cm[r] = v;
+        }
+        if (l31 == 0) {
+          uint4* rp = reinterpret_cast<uint4*>(red + wc * 128 + wr * 32 + 16 * hi);
+          rp[0] = make_uint4(cm[0], cm[1], cm[2], cm[3]);
+          rp[1] = make_uint4(cm[4], cm[5], cm[6], cm[7]);
+        }
+      }
+      continue;
+    }
     const uint32_t Aw = A;
     if (xe.mode == 2) A = Aall;
     uint32_t listed = 0u, flagged_total = 0u, lbase = 0u;
@@ -854,6 +988,10 @@ void k_centroid_scores_stream(const uint16_t* __restrict__ cent, const uint16_t*
     }
     s1_writeout<2, true, 4>(cur, tidv, (int64_t)tn * 128, (int64_t)t * 128, t, S, C, Ntot, Qp, S8, cmax, nch, ex, G);
   }
+  if (DIRECT) {   // the last tile's column maxima
+    __syncthreads();
+    flush_cmax(t_end - 1, (uint32_t)((t_end - 1 - t_first) & 1) * (uint32_t)S1_BUF);
+  }
 }
 
 int fpk_centroid_scores(const FpIndexDev& ix, const uint16_t* qpad, uint16_t* S, int B, int Qp, uint8_t* S8, uint16_t* cmax,
@@ -881,18 +1019,23 @@ int fpk_centroid_scores(const FpIndexDev& ix, const uint16_t* qpad, uint16_t* S,
     const int nrt = (int)grid.y;
     const int64_t tiles = (int64_t)nch * grid.y;
     const int nct = stream_env > 1 ? stream_env : (int)std::min<int64_t>(8, std::max<int64_t>(1, tiles / 512));
+    // the direct write-out (FpS1Exact::direct): chosen once per launch -- plain or lazy S, one 32-column group per query, no 8-bit
+    // bins.  The eager modes patch re-evaluated values into the staged tile, Qp 64 / 128 spread a query's excess over several
+    // waves: those keep the staged write-out.
+    const bool direct = exact && exact->direct && Qp == 32 && !S8 && (xe.mode == 0 || xe.mode == 3);
     const unsigned nwg = (unsigned)((nch + nct - 1) / nct) * (unsigned)nrt;
     const size_t lds = 2 * (size_t)s1_buf_bytes(D) + 512 + 8 * 2 * S1X_CAP * 2;   // 74.5 KiB (tile buffers + windows + the waves' entry / value lists; 138.5 KiB at dim 256): above the 64 KiB that need no opt-in
-    static std::atomic<uint64_t> ok128{0}, ok64{0}, ok256{0};
-    if (D == 128) fp_allow_big_lds((const void*)k_centroid_scores_stream<128>, ok128, 80 * 1024);
-    else if (D == 256) fp_allow_big_lds((const void*)k_centroid_scores_stream<256>, ok256, 144 * 1024);
-    else fp_allow_big_lds((const void*)k_centroid_scores_stream<64>, ok64, 80 * 1024);
-    if (D == 256)
-      hipLaunchKernelGGL(k_centroid_scores_stream<256>, dim3(nwg), dim3(512), lds, st, ix.centroids, qpad, S, C, Ntot, Qp, S8, cmax, nch, nct, nrt, ex, xe);
-    else if (D == 128)
-      hipLaunchKernelGGL(k_centroid_scores_stream<128>, dim3(nwg), dim3(512), lds, st, ix.centroids, qpad, S, C, Ntot, Qp, S8, cmax, nch, nct, nrt, ex, xe);
-    else
-      hipLaunchKernelGGL(k_centroid_scores_stream<64>, dim3(nwg), dim3(512), lds, st, ix.centroids, qpad, S, C, Ntot, Qp, S8, cmax, nch, nct, nrt, ex, xe);
+    static std::atomic<uint64_t> ok128{0}, ok64{0}, ok256{0}, okd128{0}, okd64{0}, okd256{0};
+#define S1_STREAM_LAUNCH(DK, DIR, OK, CAP)                                                                                                  \
+  do {                                                                                                                                     \
+    fp_allow_big_lds((const void*)k_centroid_scores_stream<DK, DIR>, OK, CAP);                                                            \
+    hipLaunchKernelGGL((k_centroid_scores_stream<DK, DIR>), dim3(nwg), dim3(512), lds, st, ix.centroids, qpad, S, C, Ntot, Qp, S8, cmax, nch, \
+                       nct, nrt, ex, xe);                                                                                                  \
+  } while (0)
+    if (D == 256) { if (direct) S1_STREAM_LAUNCH(256, true, okd256, 144 * 1024); else S1_STREAM_LAUNCH(256, false, ok256, 144 * 1024); }
+    else if (D == 128) { if (direct) S1_STREAM_LAUNCH(128, true, okd128, 80 * 1024); else S1_STREAM_LAUNCH(128, false, ok128, 80 * 1024); }
+    else { if (direct) S1_STREAM_LAUNCH(64, true, okd64, 80 * 1024); else S1_STREAM_LAUNCH(64, false, ok64, 80 * 1024); }
+#undef S1_STREAM_LAUNCH
     return 0;
   }
   const int nwc = 4;   // eight waves (4 x 2); the 2 x 2-wave layout of round 1 and the XCD-aware tile order (315 vs 297 us) are gone
