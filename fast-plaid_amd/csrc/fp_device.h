@@ -1,4 +1,4 @@
-// Device-side helpers shared by the HIP translation units (fp_kernels.hip, fp_maxsim.hip).  gfx950 only.
+// Device-side helpers shared by the HIP translation units (fp_kernels.hip, fp_index_ops.hip, fp_maxsim.hip).  gfx950 only.
 #pragma once
 #include <atomic>
 #include <hip/hip_runtime.h>

@@ -1,7 +1,7 @@
 // Host engine + C ABI (include/fastplaid.h) of the MI355X PLAID search library.
 // Replaces, for the search path, rust/search/{search,load,tensor,padding}.rs and
 // rust/utils/residual_codec.rs of the reference: index construction = upload + re-layout,
-// search_many = one batched, stream-ordered pipeline of HIP kernels (fp_kernels.hip).
+// search_many = one batched, stream-ordered pipeline of HIP kernels (fp_kernels.hip, fp_maxsim.hip).
 // No torch / tch; only the HIP runtime.
 #include <atomic>
 #include "../../include/fastplaid.h"
@@ -67,10 +67,16 @@ static thread_local uint64_t* t_ctor_gen = nullptr;
 static std::atomic<uint64_t> g_graph_replays{0};   // fp_graph_replay_count(): calls served by one hipGraphLaunch
 // fp_set_graph_replay / FP_GRAPH: on unless the environment says 0
 static std::atomic<int> g_graph_replay{[] { const char* e = getenv("FP_GRAPH"); return (e && atoi(e) == 0) ? 0 : 1; }()};
+// (DevBuf and HostBuf below free themselves and are not copyable: they are members of a Scratch, and deleting the scratch -- with
+// its index's device selected, fp_index_destroy -- frees every one of them)
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
   uint64_t* gen = t_ctor_gen;   // the owning scratch's allocation generation (nullptr: the process-wide one)
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
   void bump() {
     if (gen) ++*gen;
     else g_alloc_gen.fetch_add(1, std::memory_order_relaxed);
@@ -149,6 +155,10 @@ struct HostBuf {
   void* p = nullptr;
   size_t cap = 0;
   uint64_t* gen = t_ctor_gen;
+  HostBuf() = default;
+  HostBuf(const HostBuf&) = delete;
+  HostBuf& operator=(const HostBuf&) = delete;
+  ~HostBuf() { release(); }
   hipError_t ensure(size_t need) {
     if (need <= cap) return hipSuccess;
     if (gen) ++*gen;
@@ -268,22 +278,11 @@ struct Scratch : ScratchGen {
   int l0_poor = 0;              // consecutive batches in which level 0 let more than a quarter of the candidates through
   int l0h_poor = 0;             // ... and its hot-code form
   int sh_marks_mode = 0;        // sharded search, third exchange: 0 none, 1 near-tied documents, 2 every flagged document
+  // the graph executables, events and stream; the buffers free themselves when the scratch is deleted
   void destroy() {
-    out_all.release();
-    for (DevBuf* b : {&S8, &cmax128, &kq, &q8hist, &cut, &blkcnt2, &nsurv, &surv_off, &surv_pid, &l0_floors, &l0_F, &l0_e8, &l0_esc, &l0_ub,
-                      &l0_hist, &l0_npilot, &l0_pilot_pid, &l0_pilot_approx, &l0_pilot_idx, &l0_capprox, &l0_thr, &l0_nextra, &l0_xpid, &l0_xdst, &l0_blkx, &Ssample, &l0_gfl, &u_cnt, &spec_total, &sh_lmarks, &sh_lnmark, &sh_x, &sh_xall, &ms_uncm, &ms_cm16, &ms_unc, &ms_flags, &ms_pref, &ms_marks,
-                      &ms_nmark, &sh_rec, &sh_all, &tickets, &ms_flat, &l0_ubp, &wcol, &s1stats, &qpad_s1, &lz_state, &lz_gpid, &lz_gval, &lz_slackq})
-      b->release();
-    h_out.release();
-    h_small.release();
-    h_qin.release();
     if (graph.exec) { (void)hipGraphExecDestroy(graph.exec); graph.exec = nullptr; graph.valid = false; }
     for (auto& sh2 : shapes)
       if (sh2.graph.exec) { (void)hipGraphExecDestroy(sh2.graph.exec); sh2.graph.exec = nullptr; }
-    DevBuf* all[] = {&qin,      &qpad,     &S,        &partial, &cells,   &ucells,     &ncells,  &allow,    &subbm,  &invalid, &sub_ids,
-                     &sub_off,  &bitmap,   &blkcnt,   &ncand,   &cand_off, &cand_pid,  &approx,  &hist,     &selstate, &sel_pid, &tie_pid,
-                     &sel_approx, &sel_cnt, &exact,   &out_pid, &out_score, &out_cnt,  &tmpf,    &tmpp,     &tok_idx, &recon};
-    for (DevBuf* b : all) b->release();
     for (auto& e : ev)
       if (e) (void)hipEventDestroy(e);
     if (st) (void)hipStreamDestroy(st);
@@ -310,6 +309,8 @@ static thread_local bool g_have_ms = false;
 static thread_local int g_last_lazy = 0;      // the last fp_search batch ran S1's lazy form (1), the eager one (0), or was a replayed graph (-1)
 static thread_local uint64_t g_last_s1[4];   // FP_S1_STATS: S1's certification counters of the last call (flagged, changed, slow path, mode-2 unflagged differences)
 static bool s1_stats_enabled() { static const bool on = getenv("FP_S1_STATS") != nullptr; return on; }
+// FP_MAXSIM_REPAIR: 0 off, 1 (default) the near-tied documents, 2 every flagged document
+static int maxsim_repair_mode() { static const int v = [] { const char* e = getenv("FP_MAXSIM_REPAIR"); return e ? atoi(e) : 1; }(); return v; }
 static thread_local int64_t g_last_counts[6];  // candidates, exact-scored docs, repaired docs, sub-batches, form of S4 (0 exact / 1 8-bit bounds / 2 level 0; -1: replayed graph), lazy-S1 overflows the scratch remembers (>= 2: lazy form off)
 
 // results of one (sub-)batch in one device block: ids | scores | counts
@@ -507,8 +508,7 @@ static int finish_layout(fp_index* ix, int maxlen, hipStream_t st) {
   // S1's zero-padded view of the centroid table (FpIndexDev::cent_s1)
   D.cent_s1 = nullptr;
   D.dim_s1 = D.dim;
-  const bool pad_env = true;
-  if (pad_env && D.dim < 256 && D.dim != 64 && D.dim != 128) {
+  if (D.dim < 256 && D.dim != 64 && D.dim != 128) {
     const int dp = D.dim < 64 ? 64 : (D.dim < 128 ? 128 : 256);
     uint16_t* cp = nullptr;
     hipError_t e = hipMalloc((void**)&cp, (size_t)D.C * dp * 2 + 64);
@@ -1075,9 +1075,6 @@ static int run_front(Pipe& P, const int64_t* h_sub_ids, const int64_t* h_sub_off
   }
   // S2
   const int np = (int)std::max<int64_t>(sh.n_probe, 1);
-  int NP = 1;
-  while (NP < np) NP <<= 1;
-  (void)NP;
   HIPCHK(s->cells.ensure((size_t)B * sh.Q * np * 4));
   HIPCHK(s->ucells.ensure((size_t)B * sh.Q * np * 4));
   HIPCHK(s->ncells.ensure((size_t)B * 4));
@@ -1102,13 +1099,12 @@ static int run_front(Pipe& P, const int64_t* h_sub_ids, const int64_t* h_sub_off
   // host sync, ~30 us of idle GPU); later batches of the same shape run on with the capacity learnt so far (125 % of the largest
   // total seen) as M -- every kernel below takes its ranges from cand_off, M only sizes things.  A batch that exceeds the
   // capacity is emptied on the device (k_cand_offsets) and run again by the caller once the true total is known.
-  const bool spec_env = true;
   const int64_t key[4] = {B, sh.Q, sh.n_probe, has_subset ? 1 : 0};
   if (P.allow_spec && (s->spec_key[0] != key[0] || s->spec_key[1] != key[1] || s->spec_key[2] != key[2] || s->spec_key[3] != key[3])) {
     s->spec_cap = 0;
     for (int i = 0; i < 4; ++i) s->spec_key[i] = key[i];
   }
-  P.spec = P.allow_spec && spec_env && s->spec_cap > 0;
+  P.spec = P.allow_spec && s->spec_cap > 0;
   HIPCHK(s->spec_total.ensure(32));   // {candidate total, fp_shard_search's overflow mark (int32 at byte 8), the probe's overflow flag (int32 at byte 16)}
   int64_t* d_total = s->spec_total.as<int64_t>();
   fpk_cand_count(s->bitmap.as<uint32_t>(), has_subset ? s->subbm.as<uint32_t>() : nullptr, s->invalid.as<int32_t>(), B, P.W,
@@ -1273,10 +1269,9 @@ static int run_maxsim(fp_index* ix, Scratch* s, const FpSearchShape& sh, int64_t
   const FpIndexDev& D = ix->d;
   hipStream_t st = s->st;
   const int B = sh.B;
-  static const int repair_env = [] { const char* e = getenv("FP_MAXSIM_REPAIR"); return e ? atoi(e) : 1; }();   // 0: off, 2: every flagged document
   HIPCHK(s->exact.ensure((size_t)B * R * 4));
   HIPCHK(s->ms_pref.ensure((size_t)(B + 1) * 8));
-  const bool repair = repair_env != 0 && fpk_maxsim_fast_shape(D.dim, D.nbits);
+  const bool repair = maxsim_repair_mode() != 0 && fpk_maxsim_fast_shape(D.dim, D.nbits);
   s->ms_repairable = repair;
   FpMaxsimAux aux{nullptr, nullptr, nullptr, nullptr};
   if (repair) {
@@ -1304,7 +1299,7 @@ static int run_maxsim(fp_index* ix, Scratch* s, const FpSearchShape& sh, int64_t
       HIPCHK(s->ms_flat.ensure((size_t)B * R * 8));
       flat_n = s->tickets.as<uint32_t>() + (2 * B + 2);
     }
-    const bool marked = mode == 1 && repair_env != 2 &&
+    const bool marked = mode == 1 && maxsim_repair_mode() != 2 &&
                         fpk_final_mark(s->exact.as<float>(), aux.unc, aux.uncm, s->sel_cnt.as<int32_t>(), R, B, top_k, s->ms_marks.as<int32_t>(),
                                        s->ms_nmark.as<int32_t>(), st, flat_n, flat_n ? s->ms_flat.p : nullptr) == 0;
     s->ms_have_marks = false;
@@ -2129,7 +2124,6 @@ extern "C" int fp_shard_begin(const fp_index* cix, const uint16_t* queries, int3
   if (int rc = validate_search(cix, nq, Q, dim, p)) return rc;
   fp_index* ix = const_cast<fp_index*>(cix);
   if (nq < 1) return fail(FP_EINVAL, "need at least one query");
-  const int64_t R = std::max<int64_t>(p->n_full_scores / 4, 1);
   HIPCHK(fp_set_device(ix->device));
   Scratch* s = acquire(ix);
   if (!s) return fail(FP_EHIP, "could not create a HIP stream");
@@ -2138,7 +2132,6 @@ extern "C" int fp_shard_begin(const fp_index* cix, const uint16_t* queries, int3
   c->P = Pipe{};
   c->P.ix = ix; c->P.s = s; c->P.sh = make_shape(nq, Q, p);
   c->empty_all = (p->n_ivf_probe > ix->d.C) || p->top_k == 0 || ix->d.N == 0;
-  (void)R;
   hipError_t e = s->qin.ensure((size_t)nq * Q * ix->d.dim * 2);
   if (e == hipSuccess) e = hipMemcpyAsync(s->qin.p, queries, (size_t)nq * Q * ix->d.dim * 2, hipMemcpyHostToDevice, s->st);
   if (e != hipSuccess) {
@@ -2209,11 +2202,10 @@ extern "C" int fp_shard_stage2(fp_shard_ctx* c, const void* dev_all_rec1, int32_
 // without looking at what its own stages did): 0 no repair at all, 1 near-tied documents, 2 every flagged document (also when R
 // is beyond the LDS of the marking kernel)
 static int shard_marks_mode(int64_t R) {
-  static const int repair_env = [] { const char* e = getenv("FP_MAXSIM_REPAIR"); return e ? atoi(e) : 1; }();
-  if (repair_env == 0) return 0;
+  if (maxsim_repair_mode() == 0) return 0;
   int np2 = 2;
   while (np2 < R) np2 <<= 1;
-  return (repair_env != 2 && np2 <= 8192) ? 1 : 2;
+  return (maxsim_repair_mode() != 2 && np2 <= 8192) ? 1 : 2;
 }
 // union + near-tie marking (identical on every rank) + repair of the marked documents this rank holds -> dev_x [B][R] f32
 static int shard_mark_and_repair(fp_index* ix, Scratch* s, const FpSearchShape& sh, const void* all_rec2, int G, int rank, bool empty_local,
@@ -2234,10 +2226,9 @@ static int shard_mark_and_repair(fp_index* ix, Scratch* s, const FpSearchShape& 
   float* u_uncm = u_score + (size_t)3 * B * R;
   if (fpk_shard_union(all_rec2, G, B, R, s->tmpp.as<int64_t>(), u_score, u_src, u_unc, u_uncm, s->u_cnt.as<int32_t>(), st))
     return fail(FP_EUNSUPPORTED, "n_ranks * max(n_full_scores/4, 1) is too large for the LDS merge of the sharded search (limit 16384 entries)");
-  static const int repair_env = [] { const char* e = getenv("FP_MAXSIM_REPAIR"); return e ? atoi(e) : 1; }();
   s->sh_marks_mode = 0;   // 0 nothing to exchange, 1 near-tied documents (marks), 2 every flagged document
-  if (repair_env != 0) {
-    s->sh_marks_mode = (repair_env != 2 && fpk_final_mark(u_score, u_unc, u_uncm, s->u_cnt.as<int32_t>(), R, B, K, s->ms_marks.as<int32_t>(),
+  if (maxsim_repair_mode() != 0) {
+    s->sh_marks_mode = (maxsim_repair_mode() != 2 && fpk_final_mark(u_score, u_unc, u_uncm, s->u_cnt.as<int32_t>(), R, B, K, s->ms_marks.as<int32_t>(),
                                                           s->ms_nmark.as<int32_t>(), st) == 0) ? 1 : 2;
     const int32_t* marks = s->sh_marks_mode == 1 ? s->ms_marks.as<int32_t>() : nullptr;
     fpk_shard_local_marks(marks, s->ms_nmark.as<int32_t>(), u_unc, s->u_cnt.as<int32_t>(), u_src, B, R, rank, s->sh_lmarks.as<int32_t>(),
@@ -2555,7 +2546,7 @@ extern "C" int fp_shard_search(const fp_index* cix, fp_comm* comm, const uint16_
 
 
 // ------------------------------------------------------------------------------------------
-// exhaustive arithmetic self-test (see fp_kernels.hip k_selftest_arith)
+// exhaustive arithmetic self-test (see fp_index_ops.hip k_selftest_arith)
 // ------------------------------------------------------------------------------------------
 extern "C" int fp_selftest_arith(int device_id, uint64_t* out_mismatches /*[16]*/) {
   if (!out_mismatches) return fail(FP_EINVAL, "null argument");

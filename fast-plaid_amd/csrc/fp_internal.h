@@ -1,4 +1,4 @@
-// Internal declarations shared by the HIP kernels (fp_kernels.hip, fp_synth.hip) and the
+// Internal declarations shared by the HIP kernels (fp_kernels.hip, fp_index_ops.hip, fp_maxsim.hip, fp_synth.hip) and the
 // host engine (fp_engine.cpp).  Not part of the C ABI (see include/fastplaid.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -11,6 +11,7 @@
 #define FP_MAX_CELLS 8192        // q_len * n_ivf_probe cap (LDS sort of probed cells)
 #define FP_MAX_SORT 16384        // entries the LDS bitonic sort handles (R, or G*R when sharded): 8 B keys, 128 KiB of LDS
 #define FP_SEL_BINS 2048
+#define FP_L0_RANGE (1ll << 17)  // centroids per range of level 0's byte table: one range = one LDS slice (FpIndexDev::n_ranges)
 
 // Device-resident index (all pointers are device memory).  Layout in HBM:
 //   centroids  [C][D]      f16   row-major
@@ -121,7 +122,7 @@ static inline unsigned fp_grid_cap(int64_t blocks, int block_size) {
   return (unsigned)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
 }
 
-// ---- launch wrappers implemented in fp_kernels.hip -----------------------------------------
+// ---- launch wrappers implemented in fp_kernels.hip and (from "misc" on) fp_index_ops.hip -----
 // All run on `st`; none synchronises.
 // padded query length: Q rounded up to a multiple of 32 (zero rows appended) -- and to 128 for 64 < Q <= 128, so that a query's
 // column groups fill whole 128-column S1 tiles and level 0's excess byte can be summed inside one tile (round 4: queries of 65 ..
@@ -240,6 +241,11 @@ void fpk_cand_count(const uint32_t* bitmap, const uint32_t* subbm, const int32_t
                     uint32_t* tickets = nullptr /*[B + 1] zeroed counters -> one launch instead of three*/,
                     const int32_t* probe_flag = nullptr);
 int fpk_cand_words_per_block();   // bitmap words one workgroup of the candidate counting / compaction kernels covers
+// the tail of every count -> scan -> offsets chain (candidates, survivors of the two bound stages): exclusive scan of blkcnt per
+// query into ncand (and of blkcnt2 into ncand2, nullable), then cand_off [B + 1].  ticket (nullable, zeroed): the scanning
+// workgroup that finishes last writes the offsets -- one launch instead of two
+void fpk_cand_scan_offsets(int32_t* blkcnt, int nblk, int32_t* ncand, int32_t* blkcnt2, int32_t* ncand2, uint32_t* ticket, int B,
+                           int64_t* cand_off, int64_t cap, int32_t* invalid, int64_t* total_out, const int32_t* probe_flag, hipStream_t st);
 void fpk_cand_compact(const uint32_t* bitmap, const uint32_t* subbm, const int32_t* invalid, int B, int64_t W,
                       const int32_t* blkcnt /*exclusive-scanned*/, int nblk, const int64_t* cand_off, int32_t* cand_pid,
                       hipStream_t st);

@@ -1369,9 +1369,9 @@ static void launch_maxsim6(const FpIndexDev& ix, const uint16_t* qpad, const FpS
   };
   const float eps_env = 1.9073486e-06f;   // 2^-19
   const float eps_rel = eps_env * (ix.dim > 128 ? (float)ix.dim / 128.f : 1.f);   // (the window was measured at dim 128; the reorder noise grows with the number of terms)
-  const int xcd = 0;   // (a query's documents on one XCD: measured -1 us, round 3)
+  // (the last field, xcd = 0: a query's documents on one XCD measured -1 us, round 3)
   MsArgs a{ix.centroids, ix.lut, ix.codes, ix.norms, ix.residuals, ix.doc_off, qpad, sel_pid, pref, exact, aux.cm16, aux.unc, aux.uncm, aux.flags,
-           Rcap, sh.B, sh.Q, sh.Qp, 0, 0, eps_rel, ix.rinv, xcd};
+           Rcap, sh.B, sh.Q, sh.Qp, 0, 0, eps_rel, ix.rinv, 0};
   static std::atomic<uint64_t> ok1{0}, ok2{0};
   fp_allow_big_lds((const void*)k_maxsim6<KS4, NBITS, 1>, ok1, 96 * 1024);
   fp_allow_big_lds((const void*)k_maxsim6<KS4, NBITS, 2>, ok2, 112 * 1024);
