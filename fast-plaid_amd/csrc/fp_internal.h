@@ -96,6 +96,29 @@ static inline __host__ __device__ constexpr int fp_resid_logical(int p, int nbit
   return (4 * (pu - start) + g) * nbits + p % nbits;
 }
 
+// k_ivf_mark reads a list's entries [lo, lo + len) of ivf_pids as ALIGNED 4-entry vectors (16-byte loads).  Host and device: the
+// stand-alone tools/probe/ivf_vec_check.hip exhausts these, and the search below, against the scalar definitions.
+//   fp_ivf_nvec   vectors that overlap the range (0 for an empty one)
+//   fp_ivf_vec    index, in vectors from the array's start, of the range's vector number i
+//   fp_ivf_r0     index of that vector's entry 0 relative to lo: -3 .. len - 1
+//   fp_ivf_keep   entry e (0 .. 3) of a vector with that r0 lies inside the range
+__host__ __device__ static inline uint32_t fp_ivf_nvec(long long lo, uint32_t len) {
+  return len ? (uint32_t)(((lo + (long long)len + 3) >> 2) - (lo >> 2)) : 0u;
+}
+__host__ __device__ static inline long long fp_ivf_vec(long long lo, uint32_t i) { return (lo >> 2) + (long long)i; }
+__host__ __device__ static inline int fp_ivf_r0(long long lo, uint32_t i) { return (int)((fp_ivf_vec(lo, i) << 2) - lo); }
+__host__ __device__ static inline bool fp_ivf_keep(int r0, int e, uint32_t len) { return (uint32_t)(r0 + e) < len; }
+// The first index in [l, h) of the ascending list p whose entry is >= target (h if none).  A plain binary search: a 4-ary one (5
+// steps of 3 independent probes against 10 of 1) was SLOWER, and a bracket around the position an evenly spread list would hold
+// the target at gained 3 % (profiles/r09_ivf_mark.txt).
+__host__ __device__ static inline long long fp_ivf_lower_bound(const int32_t* __restrict__ p, long long l, long long h, int32_t target) {
+  while (l < h) {
+    const long long m = (l + h) >> 1;
+    if (p[m] < target) l = m + 1; else h = m;
+  }
+  return l;
+}
+
 // A HIP dispatch carries its grid size in work-items as a 32-bit number: blocks * block_size must
 // stay below 2^32, a larger launch silently wraps (seen at 10 M documents: 5.1e9 work-items).
 // Kernels whose natural grid scales with the index take this cap and walk a grid-stride loop.

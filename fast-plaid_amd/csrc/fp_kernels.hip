@@ -1899,35 +1899,46 @@ void fpk_subset_prepare(const FpIndexDev& ix, const int64_t* sub_ids, const int6
 //              tiles: lists are short and L2-resident);
 // search == 1: each list's sub-range for this tile is found by binary search first (many
 //              tiles / long lists).
+// The stream is one of aligned 4-entry vectors (16-byte loads): a cell with entries [lo, hi) contributes the vectors
+// lo >> 2 .. (hi + 3) >> 2 of ivf_pids, none when hi <= lo, and a lane keeps an entry only if its index lies in [lo, hi) AND its
+// value in the tile (a vector's other entries belong to the same list outside the tile, or to a neighbouring list that was not
+// probed).  The last vector of the array may reach up to three entries past the end of ivf_pids:
+// both allocation sites (dev_alloc in fp_engine.cpp, fps_build_ivf in fp_synth.hip) pad by 64 bytes, nothing is clamped here.
 #define MARK_TILE_WORDS_MAX 8192   // 32 KiB of LDS bitmap = 262144 documents per tile
-__global__ __launch_bounds__(1024) void k_ivf_mark(const int32_t* __restrict__ ucells, const int32_t* __restrict__ ncells,
-                                                   int maxcells /*cells per pass (LDS capacity)*/, int ucstride /*row stride of ucells*/,
-                                                   const int64_t* __restrict__ ivf_off,
-                                                   const int32_t* __restrict__ ivf_pids, int64_t P, uint32_t* __restrict__ bitmap,
-                                                   int64_t W, int search, int tw) {
+#define MARK_NT 512                // threads per workgroup: 8 waves, so that FOUR workgroups fill a CU's 32 wave slots
+#define MARK_U 8                   // 16-byte vectors per lane and round of the walk
+typedef int32_t mark_i32x4 __attribute__((ext_vector_type(4)));   // one aligned 16-byte load
+// (the search and the vector arithmetic -- fp_ivf_lower_bound, fp_ivf_nvec, fp_ivf_vec, fp_ivf_r0, fp_ivf_keep -- are in fp_internal.h, where a
+// host program can check them)
+__global__ __launch_bounds__(MARK_NT, 8) void k_ivf_mark(const int32_t* __restrict__ ucells, const int32_t* __restrict__ ncells,
+                                                      int maxcells /*cells per pass (LDS capacity)*/, int ucstride /*row stride of ucells*/,
+                                                      const int64_t* __restrict__ ivf_off,
+                                                      const int32_t* __restrict__ ivf_pids, int64_t P, uint32_t* __restrict__ bitmap,
+                                                      int64_t W, int search, int tw /*a multiple of 4*/) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint32_t* tile = reinterpret_cast<uint32_t*>(smem);                              // [tw]
-  long long* lo_s = reinterpret_cast<long long*>(smem + (size_t)tw * 4);      // [maxcells]
-  uint32_t* pre = reinterpret_cast<uint32_t*>(smem + (size_t)tw * 4 + (size_t)maxcells * 8);  // [maxcells + 1]
-  __shared__ uint32_t s_scan[1024];
+  long long* lo_s = reinterpret_cast<long long*>(smem + (size_t)tw * 4);      // [maxcells] first entry
+  uint32_t* len_s = reinterpret_cast<uint32_t*>(smem + (size_t)tw * 4 + (size_t)maxcells * 8);   // [maxcells] entries
+  uint32_t* pre = len_s + maxcells;                                           // [maxcells + 1] exclusive prefix of the VECTOR counts
+  __shared__ uint32_t s_wt[16];
   const int b = blockIdx.y;
   const int tid = threadIdx.x;
   const int64_t word0 = (int64_t)blockIdx.x * tw;
   const int32_t tile_lo = (int32_t)(word0 * 32);
   const int64_t tile_hi64 = (word0 + tw) * 32;
   const int32_t tile_hi = tile_hi64 > 0x7FFFFFFF ? 0x7FFFFFFF : (int32_t)tile_hi64;
-  for (int i = tid; i < tw; i += 1024) tile[i] = 0u;
+  for (int i = tid * 4; i < tw; i += MARK_NT * 4) *reinterpret_cast<uint4*>(tile + i) = make_uint4(0u, 0u, 0u, 0u);
   const int nc_all = ncells[b];
   const int lane = tid & 63, wave = tid >> 6;
   // the probed cells are walked in chunks of at most `maxcells` (the LDS arrays' capacity)
   for (int cb = 0; cb < nc_all; cb += maxcells) {
   const int nc = (nc_all - cb) < maxcells ? (nc_all - cb) : maxcells;
   __syncthreads();   // the previous chunk's lo_s / pre are no longer read
-  // phase 1: per-cell [lo, lo+len) and exclusive prefix of the lengths.  With the per-tile range search, TWO threads per cell: one
-  // finds the list's first entry >= tile_lo, its neighbour the first >= tile_hi (the two searches one after the other were ~20
-  // dependent L2 round trips, a quarter of this workgroup's life)
+  // phase 1: per-cell [lo, lo+len) and exclusive prefix of the vector counts.  With the per-tile range search, TWO threads per
+  // cell: one finds the list's first entry >= tile_lo, its neighbour the first >= tile_hi (the two searches one after the other
+  // were twice the dependent L2 round trips)
   uint32_t base = 0;
-  const int cpr = search ? 512 : 1024;            // cells per round
+  const int cpr = search ? MARK_NT / 2 : MARK_NT;   // cells per round
   const int sl = search ? (tid >> 1) : tid;       // this thread's cell slot in the round
   const int which = search ? (tid & 1) : 0;
   for (int start = 0; start < nc; start += cpr) {
@@ -1938,12 +1949,7 @@ __global__ __launch_bounds__(1024) void k_ivf_mark(const int32_t* __restrict__ u
       const int32_t cell = ucells[(int64_t)b * ucstride + cb + j];
       if (cell >= 0 && cell < P) {
         long long beg = ivf_off[cell], end = ivf_off[cell + 1];
-        if (search) {
-          const int32_t target = which ? tile_hi : tile_lo;
-          long long l = beg, h = end;
-          while (l < h) { long long m = (l + h) >> 1; if (ivf_pids[m] < target) l = m + 1; else h = m; }
-          beg = l;   // which == 0: the range's start; which == 1: its end
-        }
+        if (search) beg = fp_ivf_lower_bound(ivf_pids, beg, end, which ? tile_hi : tile_lo);   // which == 0: the range's start; which == 1: its end
         lo = beg;
         len = (uint32_t)(end - beg);
       }
@@ -1952,71 +1958,86 @@ __global__ __launch_bounds__(1024) void k_ivf_mark(const int32_t* __restrict__ u
       const long long other = (long long)(((unsigned long long)(uint32_t)__shfl_xor((int)(uint32_t)((unsigned long long)lo >> 32), 1, 64) << 32) |
                                           (unsigned long long)(uint32_t)__shfl_xor((int)(uint32_t)lo, 1, 64));
       len = (which == 0 && j < nc) ? (uint32_t)(other - lo) : 0u;
-      if (which == 0) s_scan[sl] = len; else s_scan[512 + sl] = 0u;
-    } else {
-      s_scan[tid] = len;
     }
-    if (which == 0 && j < nc) lo_s[j] = lo;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-      uint32_t v = (tid >= off) ? s_scan[tid - off] : 0u;
-      __syncthreads();
-      s_scan[tid] += v;
-      __syncthreads();
-    }
-    if (which == 0 && j < nc) pre[j] = base + s_scan[sl] - len;
-    const uint32_t tot = s_scan[1023];
-    __syncthreads();
+    const uint32_t nvec = fp_ivf_nvec(lo, len);
+    if (which == 0 && j < nc) { lo_s[j] = lo; len_s[j] = len; }
+    uint32_t tot;
+    const uint32_t incl = fp_block_scan_incl<uint32_t>(nvec, s_wt, &tot);   // (its barriers also publish lo_s / len_s)
+    if (which == 0 && j < nc) pre[j] = base + incl - nvec;
     base += tot;
   }
   if (tid == 0) pre[nc] = base;
   __syncthreads();
   const uint32_t total = base;
-  // phase 2: walk the concatenated stream, 512 elements per wave-chunk
-  for (uint32_t c0 = (uint32_t)wave * 512u; c0 < total; c0 += 16u * 512u) {
+  // phase 2: walk the concatenated stream of vectors, 64 * MARK_U of them per wave-chunk
+  const mark_i32x4* __restrict__ pv = reinterpret_cast<const mark_i32x4*>(ivf_pids);
+  for (uint32_t c0 = (uint32_t)wave * (64u * MARK_U); c0 < total; c0 += (MARK_NT / 64) * (64u * MARK_U)) {
     int cell = 0;
     {  // last cell with pre[cell] <= c0
       int l = 0, h = nc;
       while (h - l > 1) { int m = (l + h) >> 1; if (pre[m] <= c0) l = m; else h = m; }
       cell = l;
     }
-    int32_t pid[8];
+    mark_i32x4 v[MARK_U];
+    uint32_t keep = 0u;   // bit 4 k + e: entry e of slot k lies inside its cell's [lo, lo + len)
+    static_assert(MARK_U <= 8, "one keep bit per entry of a round");
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
+    for (int k = 0; k < MARK_U; ++k) {
       const uint32_t g = c0 + (uint32_t)k * 64u + (uint32_t)lane;
-      pid[k] = -1;
+      v[k] = mark_i32x4{-1, -1, -1, -1};
       if (g < total) {
         while (g >= pre[cell + 1]) ++cell;
-        pid[k] = ivf_pids[lo_s[cell] + (long long)(g - pre[cell])];
+        const long long lo = lo_s[cell];
+        const uint32_t i = g - pre[cell], len = len_s[cell];
+        v[k] = pv[fp_ivf_vec(lo, i)];
+        const int r0 = fp_ivf_r0(lo, i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) keep |= fp_ivf_keep(r0, e, len) ? 1u << (4 * k + e) : 0u;
       }
     }
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int32_t p = pid[k];
-      if (p >= tile_lo && p < tile_hi) atomicOr(&tile[(p - tile_lo) >> 5], 1u << (p & 31));
+    for (int k = 0; k < MARK_U; ++k) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int32_t p = v[k][e];
+        if ((keep >> (4 * k + e) & 1u) && p >= tile_lo && p < tile_hi) atomicOr(&tile[(p - tile_lo) >> 5], 1u << (p & 31));
+      }
     }
   }
   }
   __syncthreads();
   // phase 3: write the tile (W is a multiple of 64 words; tiles may overhang the end)
   uint32_t* dst = bitmap + (int64_t)b * W + word0;
-  for (int i = tid * 4; i < tw; i += 4096) {
+  for (int i = tid * 4; i < tw; i += MARK_NT * 4) {
     if (word0 + i < W) *reinterpret_cast<uint4*>(dst + i) = *reinterpret_cast<const uint4*>(tile + i);
   }
 }
 
 void fpk_ivf_mark(const FpIndexDev& ix, const int32_t* ucells, const int32_t* ncells, int ucstride, int B, uint32_t* bitmap,
                   int64_t W, hipStream_t st) {
-  const int maxcells = ucstride < FP_MAX_CELLS ? ucstride : FP_MAX_CELLS;   // probed cells per pass of the kernel
-  // tile size: the largest that still gives the chip ~4 workgroups per CU (measured at cfg2: B=64 -> 2048 words 0.11 ms vs 8192 words 0.26 ms; B=8 -> 512 words 0.04 vs 0.22 ms)
+  // tests: FP_TEST=ivf_tw=<words> forces the tile width (a multiple of 4, at least 16), ivf_maxcells=<n> caps the cells per pass
+  static const int tw_env = (int)fp_test_opt("ivf_tw", 0), mc_env = (int)fp_test_opt("ivf_maxcells", 0);
+  // tile size: the largest that still gives the chip 1024 workgroups, which is what it holds at once -- a workgroup is 8 waves, a
+  // CU has 32 wave slots (4 SIMDs x 8 at <= 64 VGPRs), 256 CUs x 4.  More tiles than that run in a second residency round, fewer
+  // leave wave slots empty while every workgroup's chain of dependent loads is as long as ever (cfg2, B = 64: 1024 words 65.8 us,
+  // 2048 words 47.7, 4096 words 194.5; with 1024-thread workgroups, two per CU, 2048 words took 56.2 and the parent's scalar walk
+  // 79.7).  What the 47.9 us are now, by timing-only ablation: the binary searches 17, the walk's LDS bookkeeping 17, list loads
+  // and atomics 7, the rest 6 -- profiles/r09_ivf_mark.txt, which also has what did NOT pay (a 4-ary search: slower).
   int tw = MARK_TILE_WORDS_MAX;
   while (tw > 512 && ((W + tw - 1) / tw) * B < 1024) tw >>= 1;
+  if (tw_env >= 16 && tw_env <= MARK_TILE_WORDS_MAX && tw_env % 4 == 0) tw = tw_env;
   const int ntile = (int)((W + tw - 1) / tw);
-  const size_t lds = (size_t)tw * 4 + (size_t)maxcells * 8 + (size_t)(maxcells + 1) * 4 + 16;
+  // probed cells per pass of the kernel: 16 bytes of LDS each beside the tile, within the 144 KiB asked for below
+  int maxcells = ucstride < FP_MAX_CELLS ? ucstride : FP_MAX_CELLS;
+  const int room = (144 * 1024 - tw * 4 - 128) / 16;
+  if (maxcells > room) maxcells = room;
+  if (mc_env > 0 && mc_env < maxcells) maxcells = mc_env;
+  if (maxcells < 1) maxcells = 1;
+  const size_t lds = (size_t)tw * 4 + (size_t)maxcells * 12 + (size_t)(maxcells + 1) * 4 + 16;
   static std::atomic<uint64_t> lds_ok{0};
   fp_allow_big_lds((const void*)k_ivf_mark, lds_ok, 144 * 1024);
   const int search = ntile > 8 ? 1 : 0;
-  hipLaunchKernelGGL(k_ivf_mark, dim3((unsigned)ntile, (unsigned)B), dim3(1024), lds, st, ucells, ncells, maxcells, ucstride, ix.ivf_off,
+  hipLaunchKernelGGL(k_ivf_mark, dim3((unsigned)ntile, (unsigned)B), dim3(MARK_NT), lds, st, ucells, ncells, maxcells, ucstride, ix.ivf_off,
                      ix.ivf_pids, ix.P, bitmap, W, search, tw);
 }
 
