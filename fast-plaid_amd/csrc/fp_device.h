@@ -1,4 +1,5 @@
-// Device-side helpers shared by the HIP translation units (fp_kernels.hip, fp_index_ops.hip, fp_maxsim.hip).  gfx950 only.
+// Device-side helpers shared by the HIP translation units (fp_kernels.hip, fp_index_ops.hip, fp_maxsim.hip, fp_synth.hip,
+// fp_kmeans.hip).  gfx950 only.
 #pragma once
 #include <atomic>
 #include <hip/hip_runtime.h>
@@ -8,6 +9,18 @@ typedef _Float16 half_t;
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef float f16v __attribute__((ext_vector_type(16)));
+
+// The counter hash of the synthetic generator and of the k-means reseed (synth.py mix64 / stream_key / rnd): every integer is a
+// pure function of (seed, stream, counter) through the splitmix64 finaliser.
+__host__ __device__ static inline uint64_t mix64(uint64_t x) {
+  uint64_t z = x + 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+__host__ __device__ static inline uint64_t stream_key(uint64_t seed, uint64_t stream) {
+  return mix64(seed * 0xD1342543DE82EF95ull + stream);
+}
 
 #define NEG_MASK_F (-10000.0f)  // masked_fill(-9999.0) stored in fp16 (search.rs:395)
 

@@ -2105,6 +2105,163 @@ extern "C" int fp_assign_l2(int device_id, const uint16_t* centroids, const floa
   return FP_OK;
 }
 
+// k-means trainer (fastplaid.h fp_kmeans): the sample goes up once, every Lloyd iteration runs on the device; per iteration only the
+// chunks' overflow counters of the MFMA narrowing come back (a chunk with a non-zero counter is assigned again by the exact kernel).
+enum { KM_UPLOAD, KM_ASSIGN, KM_INDEX, KM_SUM, KM_FINALISE, KM_NARROWED, KM_FALLBACK, KM_N };   // five times, two chunk counts
+static thread_local float g_km_ms[KM_N];
+static thread_local int g_km_have = 0;   // iterations the figures of the last call cover (0: none)
+extern "C" int fp_kmeans_last_timings(float* ms, int cap) {
+  for (int i = 0; i < std::min(cap, (int)KM_N); ++i) ms[i] = g_km_ms[i];
+  return g_km_have;
+}
+
+extern "C" int fp_kmeans(int device_id, const uint16_t* data, int64_t n, int32_t dim, int64_t k, int32_t niter, const int64_t* init_rows,
+                         uint64_t seed, float* out_centroids, int64_t* out_counts) {
+  g_km_have = 0;
+  if (!data || !init_rows || !out_centroids || n < 1 || k < 1 || niter < 0) return fail(FP_EINVAL, "bad argument");
+  if (dim < 1 || dim > 256) return fail(FP_EUNSUPPORTED, "fp_kmeans: dim must be in [1, 256]");
+  if (k > n) return fail(FP_EINVAL, "fp_kmeans: fewer training points (" + std::to_string(n) + ") than centroids (" + std::to_string(k) + ")");
+  if (n >= 0x7FFFFFFFll) return fail(FP_EUNSUPPORTED, "fp_kmeans: more than 2^31-2 training points");
+  for (int64_t c = 0; c < k; ++c)
+    if (init_rows[c] < 0 || init_rows[c] >= n) return fail(FP_EINVAL, "fp_kmeans: init_rows[" + std::to_string(c) + "] outside [0, n)");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(FP_EHIP, "no HIP device available (this library has no CPU path)");
+  if (device_id < 0 || device_id >= ndev) return fail(FP_EINVAL, "device index out of range");
+  HIPCHK(fp_set_device(device_id));
+  const int64_t chunk_opt = (int64_t)fp_test_opt("kmeans_chunk", 0);   // tests: a chunk boundary inside a few thousand points
+  const int64_t CHUNK = std::min<int64_t>(n, chunk_opt > 0 ? chunk_opt : (1ll << 20));
+  const int64_t nchunk = (n + CHUNK - 1) / CHUNK;
+  const bool timed = niter > 0 && niter <= 64;
+  void *d_data = nullptr, *d_init = nullptr, *d_lab = nullptr, *d_mem = nullptr, *d_c32 = nullptr, *d_c16 = nullptr, *d_hn = nullptr,
+       *d_sums = nullptr, *d_cnt = nullptr, *d_cur = nullptr, *d_cnt64 = nullptr, *d_work = nullptr, *d_over = nullptr,
+       *d_stat = nullptr;
+  hipStream_t st = nullptr;
+  std::vector<hipEvent_t> ev;
+  auto cleanup = [&]() {
+    for (void* p : {d_data, d_init, d_lab, d_mem, d_c32, d_c16, d_hn, d_sums, d_cnt, d_cur, d_cnt64, d_work, d_over, d_stat})
+      if (p) (void)hipFree(p);
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    if (st) (void)hipStreamDestroy(st);
+  };
+#define KCHK(x)                                                                                \
+  do {                                                                                         \
+    hipError_t e_ = (x);                                                                       \
+    if (e_ != hipSuccess) {                                                                    \
+      cleanup();                                                                               \
+      (void)hipGetLastError();                                                                 \
+      return fail(e_ == hipErrorOutOfMemory ? FP_ENOMEM : FP_EHIP, std::string("HIP error in fp_kmeans: ") + hipGetErrorString(e_) + " at " #x); \
+    }                                                                                          \
+  } while (0)
+  const size_t kd = (size_t)k * dim;
+  struct { void** p; size_t bytes; } bufs[] = {
+      {&d_data, (size_t)n * dim * 2}, {&d_init, (size_t)k * 8}, {&d_lab, (size_t)n * 4}, {&d_mem, (size_t)n * 4}, {&d_c32, kd * 4},
+      {&d_c16, kd * 2}, {&d_hn, (size_t)k * 4}, {&d_sums, kd * 8}, {&d_cnt, (size_t)k * 4},
+      {&d_cur, (size_t)k * 4}, {&d_cnt64, (size_t)k * 8}, {&d_work, fpk_compress_work_bytes(CHUNK)}, {&d_over, (size_t)nchunk * 4},
+      {&d_stat, 64}};
+  size_t need = 0, mfree = 0, mtotal = 0;
+  for (auto& b : bufs) need += b.bytes + 256;
+  KCHK(hipMemGetInfo(&mfree, &mtotal));
+  if (need > mfree)
+    return fail(FP_ENOMEM, "fp_kmeans: the sample and its work buffers need " + std::to_string(need) + " bytes of device memory, " +
+                               std::to_string(mfree) + " are free");
+  KCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  for (auto& b : bufs) KCHK(hipMalloc(b.p, b.bytes));
+  if (timed) {
+    ev.resize(2 + 5 * (size_t)niter, nullptr);
+    for (hipEvent_t& e : ev) KCHK(hipEventCreate(&e));
+  }
+  const uint16_t* data_d = static_cast<const uint16_t*>(d_data);
+  uint32_t* stat = static_cast<uint32_t*>(d_stat);   // [0..1] {max|cent16|, max hn} of the iteration, [4] max |x| bits of the data
+  int32_t* labels = static_cast<int32_t*>(d_lab);
+  if (timed) KCHK(hipEventRecord(ev[0], st));
+  KCHK(hipMemsetAsync(d_stat, 0, 64, st));
+  KCHK(hipMemcpyAsync(d_data, data, (size_t)n * dim * 2, hipMemcpyHostToDevice, st));
+  KCHK(hipMemcpyAsync(d_init, init_rows, (size_t)k * 8, hipMemcpyHostToDevice, st));
+  fpk_km_scan_data(data_d, n * dim, stat + 4, st);
+  uint32_t h_xmax = 0;
+  KCHK(hipMemcpyAsync(&h_xmax, stat + 4, 4, hipMemcpyDeviceToHost, st));
+  if (timed) KCHK(hipEventRecord(ev[1], st));
+  KCHK(hipStreamSynchronize(st));
+  KCHK(hipGetLastError());
+  if (h_xmax >= 0x7C00u) {
+    cleanup();
+    return fail(FP_EINVAL, "fp_kmeans: the data holds a value that is not finite");
+  }
+  // exact sums in int64 units of 2^-24: refuse what could leave 2^62
+  if ((unsigned __int128)n * (unsigned __int128)fp_f16_fixed((uint16_t)h_xmax) >= ((unsigned __int128)1 << 62)) {
+    cleanup();
+    return fail(FP_EUNSUPPORTED, "fp_kmeans: n * max|x| * 2^24 >= 2^62 (the exact fixed-point sums could overflow)");
+  }
+  fpk_km_finalise(data_d, n, dim, k, static_cast<const int64_t*>(d_init), nullptr, nullptr, seed, 0, static_cast<float*>(d_c32),
+                  static_cast<uint16_t*>(d_c16), static_cast<float*>(d_hn), stat, st);
+  std::vector<int32_t> h_over((size_t)nchunk, 0);
+  int64_t n_narrowed = 0, n_fallback = 0;   // chunk assignments through the MFMA narrowing / of those, sent on to the exact kernel
+  for (int it = 0; it < niter; ++it) {
+    hipEvent_t* e = timed ? &ev[2 + 5 * (size_t)it] : nullptr;
+    if (e) KCHK(hipEventRecord(e[0], st));
+    KCHK(hipMemsetAsync(d_over, 0, (size_t)nchunk * 4, st));
+    bool narrowed = false;
+    for (int64_t ci = 0; ci < nchunk; ++ci) {
+      const int64_t t0 = ci * CHUNK, nn = std::min<int64_t>(CHUNK, n - t0);
+      const int rc = fpk_assign_l2_narrow(data_d + t0 * dim, nn, static_cast<const uint16_t*>(d_c16), static_cast<const float*>(d_hn), stat, k, dim,
+                                          labels + t0, d_work, static_cast<int32_t*>(d_over) + ci, st);
+      if (rc < 0) {
+        cleanup();
+        return fail(FP_EUNSUPPORTED, "fp_kmeans: assignment chunk (" + std::to_string(rc) + ")");
+      }
+      narrowed |= rc == 1;
+      n_narrowed += rc == 1;
+    }
+    if (narrowed) {   // the fallback flags: the only thing that returns to the host between iterations
+      KCHK(hipMemcpyAsync(h_over.data(), d_over, (size_t)nchunk * 4, hipMemcpyDeviceToHost, st));
+      KCHK(hipStreamSynchronize(st));
+      for (int64_t ci = 0; ci < nchunk; ++ci) {
+        if (h_over[(size_t)ci] == 0) continue;   // else: a point met more than ASSIGN_CAP near-tied centroids
+        ++n_fallback;
+        const int64_t t0 = ci * CHUNK, nn = std::min<int64_t>(CHUNK, n - t0);
+        if (fpk_assign_l2_exact(data_d + t0 * dim, nn, static_cast<const uint16_t*>(d_c16), static_cast<const float*>(d_hn), k, dim, labels + t0, st)) {
+          cleanup();
+          return fail(FP_EUNSUPPORTED, "fp_kmeans: assignment chunk");
+        }
+      }
+    }
+    if (e) KCHK(hipEventRecord(e[1], st));
+    fpk_km_index(labels, n, k, static_cast<int32_t*>(d_cnt), static_cast<int32_t*>(d_cur), static_cast<int32_t*>(d_mem), st);
+    if (e) KCHK(hipEventRecord(e[2], st));
+    fpk_km_sum(data_d, n, dim, k, labels, static_cast<const int32_t*>(d_mem), static_cast<int64_t*>(d_sums), st);
+    if (e) KCHK(hipEventRecord(e[3], st));
+    fpk_km_finalise(data_d, n, dim, k, nullptr, static_cast<const int64_t*>(d_sums), static_cast<const int32_t*>(d_cnt), seed, it,
+                    static_cast<float*>(d_c32), static_cast<uint16_t*>(d_c16), static_cast<float*>(d_hn), stat, st);
+    if (e) KCHK(hipEventRecord(e[4], st));
+    KCHK(hipGetLastError());
+  }
+  KCHK(hipMemcpyAsync(out_centroids, d_c32, kd * 4, hipMemcpyDeviceToHost, st));
+  if (out_counts) {
+    if (niter > 0) {
+      fpk_km_widen_counts(static_cast<const int32_t*>(d_cnt), static_cast<int64_t*>(d_cnt64), k, st);
+      KCHK(hipMemcpyAsync(out_counts, d_cnt64, (size_t)k * 8, hipMemcpyDeviceToHost, st));
+    } else {
+      memset(out_counts, 0, (size_t)k * 8);
+    }
+  }
+  KCHK(hipStreamSynchronize(st));
+  KCHK(hipGetLastError());
+  if (timed) {
+    float ms[KM_N] = {0.f, 0.f, 0.f, 0.f, 0.f, (float)n_narrowed, (float)n_fallback}, x = 0.f;
+    KCHK(hipEventElapsedTime(&ms[KM_UPLOAD], ev[0], ev[1]));
+    for (int it = 0; it < niter; ++it)
+      for (int s = 0; s < 4; ++s) {
+        KCHK(hipEventElapsedTime(&x, ev[2 + 5 * (size_t)it + s], ev[3 + 5 * (size_t)it + s]));
+        ms[KM_ASSIGN + s] += x;
+      }
+    for (int i = 0; i < KM_N; ++i) g_km_ms[i] = ms[i];
+    g_km_have = niter;
+  }
+#undef KCHK
+  cleanup();
+  return FP_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // document-sharded search (see fastplaid.h)
 // ------------------------------------------------------------------------------------------

@@ -230,11 +230,14 @@ static size_t assign_exact_lds(int D) { return (size_t)2 * 64 * (D + 1) * 4 + 64
 // scores is always among them (see k_assign_thr) -- and k_assign_recheck evaluates only those (1-2 per token, at most
 // ASSIGN_CAP) with the ascending-k chain and the first-index tie rule.  A token that collects more than ASSIGN_CAP
 // candidates (many near-duplicate centroids) sends the whole chunk back to the exact kernel.
+// L2 = true (k-means assignment, fpk_assign_l2_narrow): the score is fl32(MFMA dot - half_sqnorm[c]); pass 1 / pass 2 / the
+// re-check work on that value and the threshold is k_assign_thr_l2's.
 #define ASSIGN_CAP 8
-template <int D, int PASS>
+template <int D, int PASS, bool L2>
 __global__ __launch_bounds__(256) void k_assign_mfma(const uint16_t* __restrict__ emb, int64_t T, const uint16_t* __restrict__ cent, int64_t C,
                                                      float* __restrict__ tmax /*PASS 1 out*/, const float* __restrict__ thr /*PASS 2 in*/,
-                                                     int32_t* __restrict__ ccnt, int32_t* __restrict__ ccand) {
+                                                     int32_t* __restrict__ ccnt, int32_t* __restrict__ ccand,
+                                                     const float* __restrict__ half_sqnorm /*L2 only*/) {
   constexpr int CH = D / 8;
   constexpr int ROWB = D * 2;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -300,11 +303,14 @@ __global__ __launch_bounds__(256) void k_assign_mfma(const uint16_t* __restrict_
     for (int b = 0; b < 2; ++b) {
       const int64_t c = c0 + wc * 64 + b * 32 + l31;
       if (c >= C) continue;
+      float hn = 0.f;
+      if constexpr (L2) hn = half_sqnorm[c];
 #pragma unroll
       for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const float v = acc[a][b][r];
+          float v = acc[a][b][r];
+          if constexpr (L2) v -= hn;
           if (PASS == 1) {
             st[a][r] = fmaxf(st[a][r], v);
           } else if (v >= st[a][r]) {
@@ -348,10 +354,37 @@ __global__ void k_assign_thr(const uint16_t* __restrict__ emb, int64_t T, int D,
   }
 }
 
+// The L2 form (k-means): score_c = fl32(dot_c - hn_c), compared in fp32.  thr[t] = M - 2 delta, M the maximum of the MFMA scores.
+// Why the exact winner w is collected.  Write e_c for the ascending chain, a_c for the MFMA sum, s_c = fl32(e_c - hn_c) for the
+// exact score and m_c = fl32(a_c - hn_c) for the MFMA score.  |a_c - e_c| <= eps = D 2^-23 l1(x) max|c| (two summation orders of
+// the same D exact products, each within (D - 1) 2^-24 sum|products| of the true sum: the figure k_assign_thr uses).  A rounded
+// difference r = fl32(z) has |r - z| <= 2^-24 |r| (a subnormal difference is exact), and every score satisfies
+// |score| <= B = (l1(x) max|c| + max hn)(1 + 2^-16), so |m_c - s_c| <= delta = eps + 2^-23 B.  With c* the argmax of the MFMA
+// scores, s_w >= s_c* (w wins the exact comparison), hence
+//   m_w >= s_w - delta >= s_c* - delta >= m_c* - 2 delta = M - 2 delta.
+// There is no fp16-ulp term: nothing is rounded to fp16 before the comparison.  The kernel takes 2^-22 B in place of 2^-23 B,
+// which covers B's factor, the rounding of thr itself (<= 2^-24 B) and of the l1 chain (relative D 2^-24, against the 1 / D
+// that D in place of D - 1 leaves in eps).  stat: {max|cent16|, max hn} as fp32 bits, reduced on the device by k_km_finalise
+// (both change with every Lloyd iteration).
+__global__ void k_assign_thr_l2(const uint16_t* __restrict__ emb, int64_t T, int D, const uint32_t* __restrict__ stat,
+                                const float* __restrict__ tmax, float* __restrict__ thr, int32_t* __restrict__ ccnt) {
+  const float cmaxabs = __uint_as_float(stat[0]), hnmax = __uint_as_float(stat[1]);
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < T; t += (int64_t)gridDim.x * blockDim.x) {
+    float l1 = 0.f;
+    for (int d = 0; d < D; ++d) l1 += __builtin_fabsf((float)__builtin_bit_cast(half_t, emb[t * D + d]));
+    const float dotmax = l1 * cmaxabs;
+    const float eps = dotmax * (float)D * 1.1920929e-07f;            // D * 2^-23 * sum|x_k| max|c|
+    const float rnd = (dotmax + hnmax) * 2.3841858e-07f;             // 2^-22 B
+    thr[t] = tmax[t] - 2.0f * (eps + rnd);
+    ccnt[t] = 0;
+  }
+}
+
 // exact evaluation of the collected candidates; codes[t] = -1 when the candidate list overflowed
+template <bool L2>
 __global__ void k_assign_recheck(const uint16_t* __restrict__ emb, int64_t T, const uint16_t* __restrict__ cent, int D,
                                  const int32_t* __restrict__ ccnt, const int32_t* __restrict__ ccand, int32_t* __restrict__ codes,
-                                 int32_t* __restrict__ overflow) {
+                                 int32_t* __restrict__ overflow, const float* __restrict__ half_sqnorm /*L2 only*/) {
   for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < T; t += (int64_t)gridDim.x * blockDim.x) {
     const int n = ccnt[t];
     if (n > ASSIGN_CAP || n < 1) {   // n < 1 cannot happen (the maximum itself passes its threshold) unless a score is NaN
@@ -365,8 +398,14 @@ __global__ void k_assign_recheck(const uint16_t* __restrict__ emb, int64_t T, co
       float acc = 0.f;
       for (int d = 0; d < D; ++d)
         acc += (float)__builtin_bit_cast(half_t, emb[t * D + d]) * (float)__builtin_bit_cast(half_t, cent[(int64_t)c * D + d]);
-      const uint16_t hv = __builtin_bit_cast(uint16_t, (half_t)acc);
-      const unsigned long long key = ((unsigned long long)mono16(hv) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)c);
+      uint32_t ord;
+      if constexpr (L2) {
+        const uint32_t fb = __float_as_uint(acc - half_sqnorm[c]);
+        ord = fb ^ ((fb >> 31) ? 0xFFFFFFFFu : 0x80000000u);   // k_assign_exact<true>'s key
+      } else {
+        ord = mono16(__builtin_bit_cast(uint16_t, (half_t)acc));
+      }
+      const unsigned long long key = ((unsigned long long)ord << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)c);
       best = key > best ? key : best;
     }
     codes[t] = (int32_t)(0xFFFFFFFFu - (uint32_t)(best & 0xFFFFFFFFull));
@@ -402,6 +441,43 @@ __global__ __launch_bounds__(256) void k_quantize_pack(const uint16_t* __restric
 // scratch: tmax / thr f32 [T], ccnt i32 [T], ccand i32 [T * ASSIGN_CAP], overflow i32 [1]  (all inside `work`, see fpk_compress_work_bytes)
 size_t fpk_compress_work_bytes(int64_t T) { return (size_t)T * (4 + 4 + 4 + 4 * ASSIGN_CAP) + 64; }
 
+// pass 1 -> threshold -> pass 2 -> re-check of one chunk on `st` (D 64 or 128); *overflow is zeroed first and counts the tokens
+// whose candidate list overflowed.  L2: the k-means score (half_sqnorm, stat = k_assign_thr_l2's device-side maxima)
+static int32_t* assign_work_overflow(void* work, int64_t T) { return reinterpret_cast<int32_t*>(static_cast<char*>(work) + (size_t)T * (12 + 4 * ASSIGN_CAP)); }
+template <int D, bool L2>
+static void assign_narrow_d(const uint16_t* emb, int64_t T, const uint16_t* cent, int64_t C, float cmaxabs, const uint32_t* stat,
+                            const float* half_sqnorm, int32_t* codes32, void* work, int32_t* overflow, hipStream_t st) {
+  float* tmax = static_cast<float*>(work);
+  float* thr = tmax + T;
+  int32_t* ccnt = reinterpret_cast<int32_t*>(thr + T);
+  int32_t* ccand = ccnt + T;
+  const unsigned mblocks = (unsigned)((T + 127) / 128);
+  const unsigned tblocks = fp_grid_cap((T + 255) / 256, 256);
+  const size_t lds = (size_t)2 * 128 * D * 2;
+  (void)hipMemsetAsync(overflow, 0, 4, st);
+  if (D == 128) {
+    static std::atomic<uint64_t> ok1{0}, ok2{0};
+    fp_allow_big_lds((const void*)k_assign_mfma<D, 1, L2>, ok1, 80 * 1024);
+    fp_allow_big_lds((const void*)k_assign_mfma<D, 2, L2>, ok2, 80 * 1024);
+  }
+  hipLaunchKernelGGL((k_assign_mfma<D, 1, L2>), dim3(mblocks), dim3(256), lds, st, emb, T, cent, C, tmax, (const float*)nullptr, (int32_t*)nullptr,
+                     (int32_t*)nullptr, half_sqnorm);
+  if (L2)
+    hipLaunchKernelGGL(k_assign_thr_l2, dim3(tblocks), dim3(256), 0, st, emb, T, D, stat, tmax, thr, ccnt);
+  else
+    hipLaunchKernelGGL(k_assign_thr, dim3(tblocks), dim3(256), 0, st, emb, T, D, cmaxabs, tmax, thr, ccnt);
+  hipLaunchKernelGGL((k_assign_mfma<D, 2, L2>), dim3(mblocks), dim3(256), lds, st, emb, T, cent, C, (float*)nullptr, thr, ccnt, ccand, half_sqnorm);
+  hipLaunchKernelGGL((k_assign_recheck<L2>), dim3(tblocks), dim3(256), 0, st, emb, T, cent, D, ccnt, ccand, codes32, overflow, half_sqnorm);
+}
+template <bool L2>
+static void assign_narrow(const uint16_t* emb, int64_t T, const uint16_t* cent, int64_t C, int D, float cmaxabs, const uint32_t* stat,
+                          const float* half_sqnorm, int32_t* codes32, void* work, int32_t* overflow, hipStream_t st) {
+  if (D == 128)
+    assign_narrow_d<128, L2>(emb, T, cent, C, cmaxabs, stat, half_sqnorm, codes32, work, overflow, st);
+  else
+    assign_narrow_d<64, L2>(emb, T, cent, C, cmaxabs, stat, half_sqnorm, codes32, work, overflow, st);
+}
+
 static int assign_codes(const uint16_t* emb, int64_t T, const uint16_t* cent, int64_t C, int D, float cmaxabs, int32_t* codes32, void* work,
                         hipStream_t st) {
   static const int impl_env = fp_test_opt("assign_exact", 0) != 0 ? 1 : 0;   // the all-VALU exact kernel only (tools/bench_compress.py)
@@ -417,29 +493,8 @@ static int assign_codes(const uint16_t* emb, int64_t T, const uint16_t* cent, in
     exact();
     return 0;
   }
-  float* tmax = static_cast<float*>(work);
-  float* thr = tmax + T;
-  int32_t* ccnt = reinterpret_cast<int32_t*>(thr + T);
-  int32_t* ccand = ccnt + T;
-  int32_t* overflow = ccand + T * ASSIGN_CAP;
-  const unsigned mblocks = (unsigned)((T + 127) / 128);
-  const size_t lds = (size_t)2 * 128 * D * 2;
-  (void)hipMemsetAsync(overflow, 0, 4, st);
-  if (D == 128) {
-    static std::atomic<uint64_t> ok1{0}, ok2{0};
-    fp_allow_big_lds((const void*)k_assign_mfma<128, 1>, ok1, 80 * 1024);
-    fp_allow_big_lds((const void*)k_assign_mfma<128, 2>, ok2, 80 * 1024);
-    hipLaunchKernelGGL((k_assign_mfma<128, 1>), dim3(mblocks), dim3(256), lds, st, emb, T, cent, C, tmax, (const float*)nullptr, (int32_t*)nullptr,
-                       (int32_t*)nullptr);
-    hipLaunchKernelGGL(k_assign_thr, dim3(fp_grid_cap((T + 255) / 256, 256)), dim3(256), 0, st, emb, T, D, cmaxabs, tmax, thr, ccnt);
-    hipLaunchKernelGGL((k_assign_mfma<128, 2>), dim3(mblocks), dim3(256), lds, st, emb, T, cent, C, (float*)nullptr, thr, ccnt, ccand);
-  } else {
-    hipLaunchKernelGGL((k_assign_mfma<64, 1>), dim3(mblocks), dim3(256), lds, st, emb, T, cent, C, tmax, (const float*)nullptr, (int32_t*)nullptr,
-                       (int32_t*)nullptr);
-    hipLaunchKernelGGL(k_assign_thr, dim3(fp_grid_cap((T + 255) / 256, 256)), dim3(256), 0, st, emb, T, D, cmaxabs, tmax, thr, ccnt);
-    hipLaunchKernelGGL((k_assign_mfma<64, 2>), dim3(mblocks), dim3(256), lds, st, emb, T, cent, C, (float*)nullptr, thr, ccnt, ccand);
-  }
-  hipLaunchKernelGGL(k_assign_recheck, dim3(fp_grid_cap((T + 255) / 256, 256)), dim3(256), 0, st, emb, T, cent, D, ccnt, ccand, codes32, overflow);
+  int32_t* overflow = assign_work_overflow(work, T);
+  assign_narrow<false>(emb, T, cent, C, D, cmaxabs, nullptr, nullptr, codes32, work, overflow, st);
   int32_t h_over = 0;
   if (hipMemcpyAsync(&h_over, overflow, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -3;
   if (h_over > 0) exact();   // a token met more than ASSIGN_CAP near-tied centroids: the whole chunk goes through the exact kernel
@@ -460,8 +515,8 @@ __global__ void k_widen_i32(const int32_t* __restrict__ in, int64_t* __restrict_
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = in[i];
 }
 
-int fpk_assign_l2(const uint16_t* emb, int64_t T, const uint16_t* cent, const float* half_sqnorm, int64_t C, int D, int32_t* codes32,
-                  int64_t* codes64, hipStream_t st) {
+int fpk_assign_l2_exact(const uint16_t* emb, int64_t T, const uint16_t* cent, const float* half_sqnorm, int64_t C, int D, int32_t* codes32,
+                        hipStream_t st) {
   if (T <= 0) return 0;
   const unsigned blocks = fp_grid_cap((T + 63) / 64, 256);
   if ((int64_t)blocks * 64 < T) return -2;
@@ -469,6 +524,26 @@ int fpk_assign_l2(const uint16_t* emb, int64_t T, const uint16_t* cent, const fl
   static std::atomic<uint64_t> ok{0};
   fp_allow_big_lds((const void*)k_assign_exact<true>, ok, 160 * 1024);
   hipLaunchKernelGGL((k_assign_exact<true>), dim3(blocks), dim3(256), assign_exact_lds(D), st, emb, T, cent, C, half_sqnorm, codes32, D);
+  return 0;
+}
+
+// k-means assignment of one chunk with the MFMA narrowing (fp_kmeans): labels for dim 64 / 128 and C >= 256, nothing read back.
+// Returns 1 when the chunk took the narrowing -- the caller reads *overflow after the stream has drained and sends a chunk with a
+// non-zero count through fpk_assign_l2_exact -- 0 when it went straight to the exact kernel, < 0 as fpk_assign_l2.
+int fpk_assign_l2_narrow(const uint16_t* emb, int64_t T, const uint16_t* cent, const float* half_sqnorm, const uint32_t* stat, int64_t C, int D,
+                         int32_t* codes32, void* work, int32_t* overflow, hipStream_t st) {
+  static const int exact_env = fp_test_opt("assign_exact", 0) != 0 ? 1 : 0;
+  if (T <= 0) return 0;
+  if (exact_env || !work || C < 256 || (D != 128 && D != 64)) return fpk_assign_l2_exact(emb, T, cent, half_sqnorm, C, D, codes32, st);
+  if ((T + 127) / 128 > 0x7FFFFFll) return -2;
+  assign_narrow<true>(emb, T, cent, C, D, 0.f, stat, half_sqnorm, codes32, work, overflow, st);
+  return 1;
+}
+
+int fpk_assign_l2(const uint16_t* emb, int64_t T, const uint16_t* cent, const float* half_sqnorm, int64_t C, int D, int32_t* codes32,
+                  int64_t* codes64, hipStream_t st) {
+  if (T <= 0) return 0;
+  if (int rc = fpk_assign_l2_exact(emb, T, cent, half_sqnorm, C, D, codes32, st)) return rc;
   hipLaunchKernelGGL(k_widen_i32, dim3(fp_grid_cap((T + 255) / 256, 256)), dim3(256), 0, st, codes32, codes64, T);
   return 0;
 }

@@ -1,4 +1,4 @@
-// Internal declarations shared by the HIP kernels (fp_kernels.hip, fp_index_ops.hip, fp_maxsim.hip, fp_synth.hip) and the
+// Internal declarations shared by the HIP kernels (fp_kernels.hip, fp_index_ops.hip, fp_kmeans.hip, fp_maxsim.hip, fp_synth.hip) and the
 // host engine (fp_engine.cpp).  Not part of the C ABI (see include/fastplaid.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -423,6 +423,32 @@ int fpk_compress(const uint16_t* emb, int64_t T, const uint16_t* cent, int64_t C
 // k-means assignment step: argmax_c (dot - half_sqnorm[c]) in fp32, ties -> lowest index
 int fpk_assign_l2(const uint16_t* emb, int64_t T, const uint16_t* cent, const float* half_sqnorm, int64_t C, int D, int32_t* codes32,
                   int64_t* codes64, hipStream_t st);
+// the same without the widening (fp_kmeans keeps 32-bit labels on the device) ...
+int fpk_assign_l2_exact(const uint16_t* emb, int64_t T, const uint16_t* cent, const float* half_sqnorm, int64_t C, int D, int32_t* codes32,
+                        hipStream_t st);
+// ... and through the MFMA narrowing (dim 64 / 128, C >= 256; else the exact kernel): see fp_index_ops.hip.  stat = device
+// {max|cent|, max half_sqnorm} as fp32 bits; work = fpk_compress_work_bytes(T); 1: narrowed, *overflow to be read by the caller
+int fpk_assign_l2_narrow(const uint16_t* emb, int64_t T, const uint16_t* cent, const float* half_sqnorm, const uint32_t* stat, int64_t C, int D,
+                         int32_t* codes32, void* work, int32_t* overflow, hipStream_t st);
+// ---- fp_kmeans.hip: the Lloyd update on the device (fp_kmeans, include/fastplaid.h) ------------
+// value of an fp16 bit pattern in units of 2^-24 (every finite fp16 value is such an integer; |v| < 2^40)
+static inline __host__ __device__ int64_t fp_f16_fixed(uint16_t h) {
+  const int e = (h >> 10) & 31, m = h & 0x3FF;
+  const int64_t v = e ? (int64_t)(m | 0x400) << (e - 1) : (int64_t)m;
+  return (h & 0x8000) ? -v : v;
+}
+// stat[0] = max over the data of (bits & 0x7FFF): >= 0x7C00 when a value is not finite (stat zeroed by the caller)
+void fpk_km_scan_data(const uint16_t* data, int64_t n_elems, uint32_t* stat, hipStream_t st);
+// cent32 / cent16 / half_sqnorm of every cluster and stat = {max|cent16|, max half_sqnorm} (zeroed here).  sums == nullptr: the
+// initial centroids data[init_rows[c]]; else the means of the exact sums, empty clusters reseeded by the counter hash
+void fpk_km_finalise(const uint16_t* data, int64_t n, int D, int64_t K, const int64_t* init_rows, const int64_t* sums, const int32_t* cnt,
+                     uint64_t seed, int it, float* cent32, uint16_t* cent16, float* half_sqnorm, uint32_t* stat, hipStream_t st);
+// inverted index of the labels (all in [0, K)): cnt [K] cluster sizes, members [n] = the clusters' lists back to back (any order inside a list); cursor [K] scratch
+void fpk_km_index(const int32_t* labels, int64_t n, int64_t K, int32_t* cnt, int32_t* cursor, int32_t* members, hipStream_t st);
+// sums [K][D] int64 in units of 2^-24 (zeroed here): exact, whatever the order
+void fpk_km_sum(const uint16_t* data, int64_t n, int D, int64_t K, const int32_t* labels, const int32_t* members, int64_t* sums,
+                hipStream_t st);
+void fpk_km_widen_counts(const int32_t* cnt, int64_t* out, int64_t K, hipStream_t st);
 // [q_len, doc_len] fp16 similarity matrices of (query, doc) hits; -1 when q_len * dim does not fit LDS
 int fpk_token_scores(const FpIndexDev& ix, const uint16_t* queries, int Q, const int32_t* hit_query, const int32_t* hit_pid, int64_t n_hits,
                      const int64_t* out_off, uint16_t* out, hipStream_t st);

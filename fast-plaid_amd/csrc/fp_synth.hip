@@ -5,6 +5,8 @@
 
 #include "fp_internal.h"
 
+#include "fp_device.h"   // mix64 / stream_key
+
 #define S_DOCLEN 1ull
 #define S_TOPIC 2ull
 #define S_TOKEN 3ull
@@ -12,15 +14,6 @@
 #define TOPIC_SIZE 8
 #define P_TOPIC_256 205ull
 
-__host__ __device__ static inline uint64_t mix64(uint64_t x) {
-  uint64_t z = x + 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-__host__ __device__ static inline uint64_t stream_key(uint64_t seed, uint64_t stream) {
-  return mix64(seed * 0xD1342543DE82EF95ull + stream);
-}
 __host__ __device__ static inline int synth_doc_len(uint64_t key_len, int doc_len, int variable, uint64_t pid) {
   if (!variable) return doc_len;
   int lo = doc_len / 4 > 1 ? doc_len / 4 : 1;

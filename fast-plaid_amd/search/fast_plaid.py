@@ -188,15 +188,15 @@ class FastPlaid:
                n_samples_kmeans: int | None = None, seed: int = 42, use_triton_kmeans: bool | None = None, metadata=None,
                compress_only: bool = False, centroids=None):
         """fast_plaid.py:398-560: k-means centroids (unless given), then the native part of the reference's create --
-        codec training, compression, IVF, directory (rust/index/create.rs)."""
-        del use_triton_kmeans
+        codec training, compression, IVF, directory (rust/index/create.rs).  use_triton_kmeans=True (the reference's switch to its
+        GPU k-means) selects the native trainer fp_kmeans; None / False keep the host loop around fp_assign_l2."""
         if metadata is not None:
             raise NotImplementedError("metadata filtering (fast_plaid.filtering) is outside the MI355X search hot path")
         if centroids is None:   # fast_plaid.py:71-185 compute_kmeans (functional equivalent, see kmeans.py)
             from .. import kmeans as _kmeans
             first = documents_embeddings[0]
             centroids = _kmeans.compute_kmeans(documents_embeddings, int(first.shape[1]), self.devices[0], kmeans_niters,
-                                               max_points_per_centroid, seed, n_samples_kmeans)
+                                               max_points_per_centroid, seed, n_samples_kmeans, native=bool(use_triton_kmeans))
         if self.index is None:
             raise ValueError("FastPlaid.create needs an index directory")
         from .. import create as _create

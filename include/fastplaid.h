@@ -244,7 +244,7 @@ int fp_token_scores(const fp_index* index, const uint16_t* queries_f16, int32_t 
  *   bucket    = #{ i : cutoffs[i] < r }                          (torch.bucketize, right=False)
  *   bytes     = each bucket as nbits bits LSB first, the bit stream packed 8 per byte big-endian.
  * Stand-alone (no index handle): host buffers in and out, processed in device-sized chunks.
- * k-means, codec training (quantiles) and file writing stay on the host (fast-plaid_amd/create.py). */
+ * Codec training (quantiles) and file writing stay on the host (fast-plaid_amd/create.py); k-means has fp_kmeans below. */
 int fp_compress(int device_id, const uint16_t* centroids_f16 /*[n_centroids, dim]*/, int64_t n_centroids, int32_t dim, int32_t nbits,
                 const uint16_t* bucket_cutoffs_f16 /*[2^nbits - 1]*/, const uint16_t* embeddings_f16 /*[n_tokens, dim]*/,
                 int64_t n_tokens, int64_t* out_codes /*[n_tokens]*/, uint8_t* out_residuals /*[n_tokens, dim*nbits/8]*/);
@@ -255,6 +255,33 @@ int fp_compress(int device_id, const uint16_t* centroids_f16 /*[n_centroids, dim
 int fp_assign_l2(int device_id, const uint16_t* centroids_f16 /*[n_centroids, dim]*/, const float* half_sqnorm /*[n_centroids]*/,
                  int64_t n_centroids, int32_t dim, const uint16_t* embeddings_f16 /*[n_tokens, dim]*/, int64_t n_tokens,
                  int64_t* out_labels /*[n_tokens]*/);
+
+/* K-means trainer (the step python/fast_plaid/search/fast_plaid.py:71-185 hands to the external fastkmeans package): the training
+ * sample is uploaded once, all `niter` Lloyd iterations run on the device, fp32 centroids come back.  The arithmetic is fixed, so
+ * the result is bit-reproducible from run to run and comparable bit for bit with a numpy restatement (tests/kmeans_model.py):
+ *   1. cent32[c] = (float)data[init_rows[c]]                       (the caller draws init_rows: the RNG protocol is the caller's)
+ *   for it = 0 .. niter-1:
+ *   2. cent16 = fp16(cent32), round to nearest even;  hn[c] = 0.5f * (ascending-d fp32 chain of cent16[c][d]^2)
+ *   3. label[t] = argmax_c fl32(chain(t, c) - hn[c]), chain = the ascending-d fp32 sum of data[t][d] * cent16[c][d], ties -> the
+ *      lowest c: what fp_assign_l2 returns for the same cent16 and hn (dim 64 / 128 with k >= 256 narrow the search with two MFMA
+ *      passes and re-check the near-ties with that chain; the labels are the same)
+ *   4. S[c][d] = the EXACT sum of data[t][d] over label[t] == c, cnt[c] the count.  Every finite fp16 value is an integer multiple
+ *      of 2^-24; the sums are int64 integers in that unit, so they do not depend on the order of the additions
+ *   5. cnt[c] > 0:  cent32[c][d] = (float)(((double)S_int * 2^-24) / (double)cnt[c]), every step round to nearest even
+ *   6. cnt[c] == 0: cent32[c] = (float)data[r], r = rnd(seed, 0x6B6D0000 + it, c) % n with the splitmix64 counter hash of the
+ *      synthetic generator (synth.rnd): mix64(mix64(seed * 0xD1342543DE82EF95 + stream) + counter)
+ * out_centroids [k, dim] f32 = cent32 after the last iteration (niter == 0: the initial rows); out_counts [k] (nullable) = cnt of
+ * the last assignment, all zero when niter == 0.  L2-normalisation and the cast to fp16 are the caller's (kmeans.compute_kmeans).
+ * Errors: FP_EINVAL for a value that is not finite, k > n, an init_rows entry outside [0, n); FP_EUNSUPPORTED for dim outside
+ * [1, 256], n >= 2^31-1, or n * max|x| * 2^24 >= 2^62 (max|x| is taken on the device; beyond it an int64 sum could overflow);
+ * FP_ENOMEM when the sample and its work buffers do not fit the device. */
+int fp_kmeans(int device_id, const uint16_t* data_f16 /*[n, dim]*/, int64_t n, int32_t dim, int64_t k, int32_t niter,
+              const int64_t* init_rows /*[k]*/, uint64_t seed, float* out_centroids /*[k, dim]*/, int64_t* out_counts /*[k] or NULL*/);
+/* Device times of the calling thread's last fp_kmeans call (HIP events, milliseconds summed over the iterations):
+ * ms[0..4] = upload + data check, assignment, inverted index, exact sums, finalise; ms[5..6] = chunk assignments that took the MFMA
+ * narrowing, and those of them that went on to the exact kernel (a candidate list overflowed).  Returns the number of iterations covered
+ * (0: none -- the call failed, ran no iteration or more than 64). */
+int fp_kmeans_last_timings(float* ms, int cap);
 
 /* ---- `reconstruct_embeddings` (rust/utils/embeddings.rs:12-69) ----------------------- */
 /* Decompresses whole documents to fp32 rows. out: host [sum(len(doc)) , dim] f32 in the
