@@ -68,6 +68,8 @@ SYMBOLS = {
     "fp_assign_l2": (C.c_int, [C.c_int, _vp, _vp, _i64, _i32, _vp, _i64, _vp]),
     "fp_kmeans": (C.c_int, [C.c_int, _vp, _i64, _i32, _i64, _i32, _vp, C.c_uint64, _vp, _vp]),
     "fp_kmeans_last_timings": (C.c_int, [_vp, C.c_int]),
+    "fp_centroid_outliers": (C.c_int, [C.c_int, _vp, _i64, _i32, _vp, _i64, C.c_float, _vp, _vp, _vp, _vp]),
+    "fp_centroid_outliers_last_counts": (C.c_int, [_vp, C.c_int]),
     "fp_maxsim_columns": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp]),
     "fp_token_scores": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _i64]),
     "fp_shard_begin": (C.c_int, [_vp, _vp, _i32, _i32, _i32, C.POINTER(FpSearchParams), C.POINTER(_vp)]),

@@ -1,5 +1,5 @@
 // Device-side helpers shared by the HIP translation units (fp_kernels.hip, fp_index_ops.hip, fp_maxsim.hip, fp_synth.hip,
-// fp_kmeans.hip).  gfx950 only.
+// fp_kmeans.hip, fp_outliers.hip).  gfx950 only.
 #pragma once
 #include <atomic>
 #include <hip/hip_runtime.h>

@@ -2262,6 +2262,147 @@ extern "C" int fp_kmeans(int device_id, const uint16_t* data, int64_t n, int32_t
   return FP_OK;
 }
 
+// Outliers of a centroid table (fastplaid.h fp_centroid_outliers): the centroids go up once, the embeddings in chunks; per chunk
+// the overflow counter of the MFMA narrowing, the data check and the outlier count come back, then that many rows.
+enum { CO_CHUNKS, CO_NARROWED, CO_FALLBACK, CO_US_UPLOAD, CO_US_ASSIGN, CO_US_OUTLIER, CO_US_DOWNLOAD, CO_N };
+static thread_local int64_t g_co[CO_N];
+static thread_local int g_co_have = 0;   // 1: the figures are those of a call that succeeded
+extern "C" int fp_centroid_outliers_last_counts(int64_t* out, int cap) {
+  for (int i = 0; i < std::min(cap, (int)CO_N); ++i) out[i] = g_co[i];
+  return g_co_have;
+}
+
+extern "C" int fp_centroid_outliers(int device_id, const uint16_t* centroids, int64_t C, int32_t dim, const uint16_t* emb, int64_t T,
+                                    float threshold_sq, int64_t* out_rows, int64_t* out_count, float* out_sqdist, int64_t* out_nearest) {
+  g_co_have = 0;
+  if (!out_count) return fail(FP_EINVAL, "bad argument");
+  *out_count = 0;
+  if (!centroids || C < 1 || T < 0 || (T > 0 && (!emb || !out_rows))) return fail(FP_EINVAL, "bad argument");
+  if (!(threshold_sq >= 0.f)) return fail(FP_EINVAL, "fp_centroid_outliers: threshold_sq must be a number >= 0");
+  if (dim < 1 || dim > 256) return fail(FP_EUNSUPPORTED, "fp_centroid_outliers: dim must be in [1, 256]");
+  if (C >= 0x7FFFFFFFll) return fail(FP_EUNSUPPORTED, "too many centroids");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(FP_EHIP, "no HIP device available (this library has no CPU path)");
+  if (device_id < 0 || device_id >= ndev) return fail(FP_EINVAL, "device index out of range");
+  HIPCHK(fp_set_device(device_id));
+  int64_t co[CO_N] = {0, 0, 0, 0, 0, 0, 0};
+  if (T == 0) {
+    for (int i = 0; i < CO_N; ++i) g_co[i] = co[i];
+    g_co_have = 1;
+    return FP_OK;
+  }
+  const int64_t chunk_opt = (int64_t)fp_test_opt("outlier_chunk", 0);   // tests: chunk boundaries inside a few thousand tokens
+  const int64_t CHUNK = std::min<int64_t>(T, chunk_opt > 0 ? chunk_opt : (1ll << 20));
+  const size_t ntile = fpk_outliers_tiles(CHUNK);
+  void *d_cent = nullptr, *d_hn = nullptr, *d_emb = nullptr, *d_lab = nullptr, *d_sq = nullptr, *d_near = nullptr, *d_flag = nullptr,
+       *d_tcnt = nullptr, *d_toff = nullptr, *d_rows = nullptr, *d_work = nullptr, *d_stat = nullptr;
+  hipStream_t st = nullptr;
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  auto cleanup = [&]() {
+    for (void* p : {d_cent, d_hn, d_emb, d_lab, d_sq, d_near, d_flag, d_tcnt, d_toff, d_rows, d_work, d_stat})
+      if (p) (void)hipFree(p);
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+    if (st) (void)hipStreamDestroy(st);
+  };
+#define OCHK(x)                                                                                \
+  do {                                                                                         \
+    hipError_t e_ = (x);                                                                       \
+    if (e_ != hipSuccess) {                                                                    \
+      cleanup();                                                                               \
+      (void)hipGetLastError();                                                                 \
+      return fail(e_ == hipErrorOutOfMemory ? FP_ENOMEM : FP_EHIP,                             \
+                  std::string("HIP error in fp_centroid_outliers: ") + hipGetErrorString(e_) + " at " #x); \
+    }                                                                                          \
+  } while (0)
+  struct { void** p; size_t bytes; } bufs[] = {
+      {&d_cent, (size_t)C * dim * 2}, {&d_hn, (size_t)C * 4}, {&d_emb, (size_t)CHUNK * dim * 2}, {&d_lab, (size_t)CHUNK * 4},
+      {&d_sq, (size_t)CHUNK * 4}, {&d_near, out_nearest ? (size_t)CHUNK * 8 : 0}, {&d_flag, (size_t)CHUNK}, {&d_tcnt, ntile * 4},
+      {&d_toff, ntile * 4}, {&d_rows, (size_t)CHUNK * 8}, {&d_work, fpk_compress_work_bytes(CHUNK)}, {&d_stat, 64}};
+  OCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  for (auto& b : bufs)
+    if (b.bytes) OCHK(hipMalloc(b.p, b.bytes));
+  for (hipEvent_t& e : ev) OCHK(hipEventCreate(&e));
+  // stat: [0..1] {max|cent|, max hn} (k_assign_thr_l2's input), [4] max |x| bits of the centroids, then of the embeddings so far,
+  // [8] the chunk's overflow counter, [9] its outlier count
+  uint32_t* stat = static_cast<uint32_t*>(d_stat);
+  const uint16_t* cent_d = static_cast<const uint16_t*>(d_cent);
+  const uint16_t* emb_d = static_cast<const uint16_t*>(d_emb);
+  const float* hn_d = static_cast<const float*>(d_hn);
+  int32_t* labels = static_cast<int32_t*>(d_lab);
+  OCHK(hipMemsetAsync(d_stat, 0, 64, st));
+  OCHK(hipMemcpyAsync(d_cent, centroids, (size_t)C * dim * 2, hipMemcpyHostToDevice, st));
+  fpk_km_scan_data(cent_d, C * dim, stat + 4, st);
+  fpk_out_prepare(cent_d, C, dim, static_cast<float*>(d_hn), stat, st);
+  uint32_t h_max = 0;
+  OCHK(hipMemcpyAsync(&h_max, stat + 4, 4, hipMemcpyDeviceToHost, st));
+  OCHK(hipStreamSynchronize(st));
+  OCHK(hipGetLastError());
+  if (h_max >= 0x7C00u) {
+    cleanup();
+    return fail(FP_EINVAL, "fp_centroid_outliers: the centroids hold a value that is not finite");
+  }
+  int64_t total = 0;
+  for (int64_t t0 = 0; t0 < T; t0 += CHUNK) {
+    const int64_t n = std::min<int64_t>(CHUNK, T - t0);
+    OCHK(hipEventRecord(ev[0], st));
+    OCHK(hipMemcpyAsync(d_emb, emb + t0 * dim, (size_t)n * dim * 2, hipMemcpyHostToDevice, st));
+    fpk_km_scan_data(emb_d, n * dim, stat + 4, st);
+    OCHK(hipEventRecord(ev[1], st));
+    const int rc = fpk_assign_l2_narrow(emb_d, n, cent_d, hn_d, stat, C, dim, labels, d_work, reinterpret_cast<int32_t*>(stat + 8), st);
+    if (rc < 0) {
+      cleanup();
+      return fail(FP_EUNSUPPORTED, "fp_centroid_outliers: assignment chunk (" + std::to_string(rc) + ")");
+    }
+    uint32_t h_chk[5] = {0, 0, 0, 0, 0};   // [0] max |x| bits, [4] overflow counter (zero when the chunk did not take the narrowing)
+    OCHK(hipMemcpyAsync(h_chk, stat + 4, sizeof(h_chk), hipMemcpyDeviceToHost, st));
+    OCHK(hipStreamSynchronize(st));
+    if (h_chk[0] >= 0x7C00u) {
+      cleanup();
+      return fail(FP_EINVAL, "fp_centroid_outliers: the embeddings hold a value that is not finite");
+    }
+    ++co[CO_CHUNKS];
+    co[CO_NARROWED] += rc == 1;
+    if (rc == 1 && h_chk[4] != 0) {   // a token met more than ASSIGN_CAP near-tied centroids: the whole chunk goes through the exact kernel
+      ++co[CO_FALLBACK];
+      if (fpk_assign_l2_exact(emb_d, n, cent_d, hn_d, C, dim, labels, st)) {
+        cleanup();
+        return fail(FP_EUNSUPPORTED, "fp_centroid_outliers: assignment chunk");
+      }
+    }
+    OCHK(hipEventRecord(ev[2], st));
+    fpk_outliers_chunk(emb_d, n, t0, cent_d, C, dim, hn_d, labels, threshold_sq, static_cast<float*>(d_sq), static_cast<int64_t*>(d_near),
+                       static_cast<uint8_t*>(d_flag), static_cast<int32_t*>(d_tcnt), static_cast<int32_t*>(d_toff),
+                       reinterpret_cast<int32_t*>(stat + 9), static_cast<int64_t*>(d_rows), st);
+    OCHK(hipEventRecord(ev[3], st));
+    int32_t h_cnt = 0;
+    OCHK(hipMemcpyAsync(&h_cnt, stat + 9, 4, hipMemcpyDeviceToHost, st));
+    OCHK(hipStreamSynchronize(st));
+    OCHK(hipGetLastError());
+    if (h_cnt < 0 || h_cnt > n) {
+      cleanup();
+      return fail(FP_EHIP, "fp_centroid_outliers: outlier count outside the chunk");
+    }
+    if (h_cnt > 0) OCHK(hipMemcpyAsync(out_rows + total, d_rows, (size_t)h_cnt * 8, hipMemcpyDeviceToHost, st));
+    if (out_sqdist) OCHK(hipMemcpyAsync(out_sqdist + t0, d_sq, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    if (out_nearest) OCHK(hipMemcpyAsync(out_nearest + t0, d_near, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    OCHK(hipEventRecord(ev[4], st));
+    OCHK(hipStreamSynchronize(st));
+    total += h_cnt;
+    for (int s = 0; s < 4; ++s) {
+      float ms = 0.f;
+      OCHK(hipEventElapsedTime(&ms, ev[s], ev[s + 1]));
+      co[CO_US_UPLOAD + s] += (int64_t)(ms * 1000.f + 0.5f);
+    }
+  }
+#undef OCHK
+  cleanup();
+  *out_count = total;
+  for (int i = 0; i < CO_N; ++i) g_co[i] = co[i];
+  g_co_have = 1;
+  return FP_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // document-sharded search (see fastplaid.h)
 // ------------------------------------------------------------------------------------------

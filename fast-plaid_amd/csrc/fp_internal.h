@@ -1,4 +1,4 @@
-// Internal declarations shared by the HIP kernels (fp_kernels.hip, fp_index_ops.hip, fp_kmeans.hip, fp_maxsim.hip, fp_synth.hip) and the
+// Internal declarations shared by the HIP kernels (fp_kernels.hip, fp_index_ops.hip, fp_kmeans.hip, fp_outliers.hip, fp_maxsim.hip, fp_synth.hip) and the
 // host engine (fp_engine.cpp).  Not part of the C ABI (see include/fastplaid.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -449,6 +449,15 @@ void fpk_km_index(const int32_t* labels, int64_t n, int64_t K, int32_t* cnt, int
 void fpk_km_sum(const uint16_t* data, int64_t n, int D, int64_t K, const int32_t* labels, const int32_t* members, int64_t* sums,
                 hipStream_t st);
 void fpk_km_widen_counts(const int32_t* cnt, int64_t* out, int64_t K, hipStream_t st);
+// ---- fp_outliers.hip: fp_centroid_outliers (include/fastplaid.h) around the assignment ---------
+// half_sqnorm[c] = 0.5f * ascending-d chain of cent[c][d]^2, stat = {max|cent|, max half_sqnorm} as fp32 bits (zeroed here)
+void fpk_out_prepare(const uint16_t* cent, int64_t C, int D, float* half_sqnorm, uint32_t* stat, hipStream_t st);
+// one chunk with its labels (all in [0, C)): sqdist [T], nearest [T] (nullable) = the labels widened, flag [T] and tilecnt / tileoff
+// [fpk_outliers_tiles(T)] scratch, *count = the flagged rows, rows[0 .. *count) = row0 + their positions, ascending
+size_t fpk_outliers_tiles(int64_t T);
+void fpk_outliers_chunk(const uint16_t* emb, int64_t T, int64_t row0, const uint16_t* cent, int64_t C, int D, const float* half_sqnorm,
+                        const int32_t* labels, float thr, float* sqdist, int64_t* nearest, uint8_t* flag, int32_t* tilecnt, int32_t* tileoff,
+                        int32_t* count, int64_t* rows, hipStream_t st);
 // [q_len, doc_len] fp16 similarity matrices of (query, doc) hits; -1 when q_len * dim does not fit LDS
 int fpk_token_scores(const FpIndexDev& ix, const uint16_t* queries, int Q, const int32_t* hit_query, const int32_t* hit_pid, int64_t n_hits,
                      const int64_t* out_off, uint16_t* out, hipStream_t st);

@@ -186,10 +186,14 @@ class FastPlaid:
 
     def create(self, documents_embeddings, kmeans_niters: int = 4, max_points_per_centroid: int = 256, nbits: int = 4,
                n_samples_kmeans: int | None = None, seed: int = 42, use_triton_kmeans: bool | None = None, metadata=None,
-               compress_only: bool = False, centroids=None):
+               compress_only: bool = False, centroids=None, *, start_from_scratch: int | None = None, batch_size: int = 25_000):
         """fast_plaid.py:398-560: k-means centroids (unless given), then the native part of the reference's create --
         codec training, compression, IVF, directory (rust/index/create.rs).  use_triton_kmeans=True (the reference's switch to its
-        GPU k-means) selects the native trainer fp_kmeans; None / False keep the host loop around fp_assign_l2."""
+        GPU k-means) selects the native trainer fp_kmeans; None / False keep the host loop around fp_assign_l2.
+        start_from_scratch=<int> keeps the raw embeddings of a corpus of at most that many documents in embeddings.npy
+        (fast_plaid.py:575-582; the reference's default is 1000), so that update(buffer_size=...) can rebuild a small index instead
+        of appending to it; None (the default) writes nothing.  batch_size is accepted for the reference's signature."""
+        del batch_size
         if metadata is not None:
             raise NotImplementedError("metadata filtering (fast_plaid.filtering) is outside the MI355X search hot path")
         if centroids is None:   # fast_plaid.py:71-185 compute_kmeans (functional equivalent, see kmeans.py)
@@ -199,6 +203,11 @@ class FastPlaid:
                                                max_points_per_centroid, seed, n_samples_kmeans, native=bool(use_triton_kmeans))
         if self.index is None:
             raise ValueError("FastPlaid.create needs an index directory")
+        if start_from_scratch is not None and len(documents_embeddings) <= start_from_scratch:   # :575-582
+            from .. import maintain
+            os.makedirs(self.index, exist_ok=True)
+            maintain.save_list_arrays(os.path.join(self.index, "embeddings.npy"),
+                                      [_to_np16(d[0] if getattr(d, "ndim", 2) == 3 else d) for d in documents_embeddings])
         from .. import create as _create
         _create.create_index(self.index, documents_embeddings, centroids, nbits=nbits, device=self.devices[0], seed=seed,
                              compress_only=compress_only)
@@ -206,28 +215,70 @@ class FastPlaid:
         self._check_and_reload_index()
         return self
 
-    def update(self, documents_embeddings, metadata=None, batch_size: int = 25_000, update_threshold_centroids: bool = False, **kwargs):
-        """fast_plaid.py update -> rust/index/update.rs: append documents with the index's existing codec.  (The reference's
-        Python layer additionally buffers small updates and may re-cluster, which needs the external usearch package;
-        here every call appends directly.)"""
-        del batch_size, kwargs
+    def update(self, documents_embeddings, metadata=None, batch_size: int = 25_000, update_threshold_centroids: bool = False, *,
+               buffer_size: int | None = None, start_from_scratch: int = 999, kmeans_niters: int = 4, max_points_per_centroid: int = 256,
+               n_samples_kmeans: int | None = None, seed: int = 42, use_triton_kmeans: bool | None = False, **kwargs):
+        """fast_plaid.py:640-713.  buffer_size=None (the default here): rust/index/update.rs alone -- the documents are appended with
+        the index's existing codec, and update_threshold_centroids folds their residual norms into cluster_threshold.npy.
+        buffer_size=<int> runs the reference's policy around that step (maintain.process_update, update.py:206-452; the reference's
+        own default is 100): an index of at most start_from_scratch documents that kept its embeddings (create(start_from_scratch=))
+        is rebuilt; small updates are appended and remembered in buffer.npy; once buffer_size documents have gathered, the embeddings
+        farther than the cluster threshold from every centroid (fp_centroid_outliers) are clustered into new centroids
+        (use_triton_kmeans selects fp_kmeans, as in create) and the buffered documents are inserted again.  The policy owns
+        update_threshold_centroids, so giving both raises ValueError."""
+        del kwargs
         if metadata is not None:
             raise NotImplementedError("metadata filtering (fast_plaid.filtering) is outside the MI355X search hot path")
-        if self.index is None or not os.path.exists(os.path.join(self.index, "metadata.json")):
-            raise FileNotFoundError("no index to update: create it first")
         from .. import maintain
-        maintain.update_index(self.index, documents_embeddings, self.devices[0], update_threshold=update_threshold_centroids)
+        if buffer_size is None:
+            del batch_size
+            if self.index is None or not os.path.exists(os.path.join(self.index, "metadata.json")):
+                raise FileNotFoundError("no index to update: create it first")
+            maintain.update_index(self.index, documents_embeddings, self.devices[0], update_threshold=update_threshold_centroids)
+            self._last_known_mtime = 0.0
+            self._check_and_reload_index()
+            return self
+        if update_threshold_centroids:
+            raise ValueError("update_threshold_centroids is set by the buffering policy: do not pass it together with buffer_size")
+        if self.index is None:
+            raise ValueError("FastPlaid.update needs an index directory")
+        from .. import kmeans as _kmeans
+
+        def reload_fn():
+            self._last_known_mtime = 0.0
+            self._check_and_reload_index()
+
+        def compute_kmeans_fn(use_triton_kmeans=None, **kw):
+            return _kmeans.compute_kmeans(native=bool(use_triton_kmeans), **kw)
+
+        def update_fn(index_path, device, embeddings, batch_size, update_threshold_centroids):
+            del batch_size
+            maintain.update_index(index_path, embeddings, device, update_threshold=update_threshold_centroids)
+
+        def format_fn(docs):   # fast_plaid.py:411-425 (+ the fp16 cast of :241, which every consumer here applies anyway)
+            return [_to_np16(d[0] if getattr(d, "ndim", 2) == 3 else d) for d in docs]
+
+        maintain.process_update(
+            index_path=self.index, devices=self.devices, indices_dict=self.indices, documents_embeddings=documents_embeddings,
+            metadata=metadata, batch_size=batch_size, kmeans_niters=kmeans_niters, max_points_per_centroid=max_points_per_centroid,
+            n_samples_kmeans=n_samples_kmeans, seed=seed, start_from_scratch=start_from_scratch, buffer_size=buffer_size,
+            use_triton_kmeans=use_triton_kmeans, create_fn=self.create, delete_fn=self.delete, compute_kmeans_fn=compute_kmeans_fn,
+            format_embeddings_fn=format_fn, update_fn=update_fn, reload_fn=reload_fn)
         self._last_known_mtime = 0.0
         self._check_and_reload_index()
         return self
 
-    def delete(self, subset: list[int], **kwargs):
-        """fast_plaid.py:1049-1100 -> rust/index/delete.rs: documents are addressed by position; survivors are renumbered."""
-        del kwargs
+    def delete(self, subset: list[int], _delete_metadata: bool = True, _delete_buffer: bool = True, **kwargs):
+        """fast_plaid.py:1049-1157 -> rust/index/delete.rs: documents are addressed by position; survivors are renumbered.  Where the
+        directory keeps raw embeddings (embeddings.npy, buffer.npy) the deleted documents leave them too (:1075-1143).  The two
+        underscore flags are the reference's: _delete_metadata concerns metadata.db, which this package does not keep, and the
+        reference itself never consults _delete_buffer."""
+        del kwargs, _delete_metadata, _delete_buffer
         if self.index is None or not os.path.exists(os.path.join(self.index, "metadata.json")):
             raise FileNotFoundError("no index to delete from")
         from .. import maintain
         maintain.delete_from_index(self.index, subset)
+        maintain.filter_kept_embeddings(self.index, subset)
         self._last_known_mtime = 0.0
         self._check_and_reload_index()
         return self

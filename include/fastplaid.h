@@ -283,6 +283,33 @@ int fp_kmeans(int device_id, const uint16_t* data_f16 /*[n, dim]*/, int64_t n, i
  * (0: none -- the call failed, ran no iteration or more than 64). */
 int fp_kmeans_last_timings(float* ms, int cap);
 
+/* Outliers of a centroid table: the tokens that lie farther than a threshold from EVERY centroid -- the device branch of
+ * python/fast_plaid/search/update.py:143-150 (x^2 + y^2 - 2 x.c^T, row minimum, compare), which decides where an index under
+ * drift needs new centroids.  Stand-alone like fp_compress / fp_assign_l2: host buffers in and out, the embeddings processed in
+ * device-sized chunks.  The arithmetic is fixed (tests/update_policy_model.py restates it); every chain below is an ascending-d
+ * fp32 sum of exact fp16 x fp16 products, so fused and unfused accumulation give the same bits:
+ *   hn[c]      = 0.5f * chain of cent[c][d]^2, on the device                            (fp_kmeans step 2, not a pairwise sum)
+ *   nearest[t] = argmax_c fl32(chain(x_t . cent_c) - hn[c]), ties -> the lowest c        (what fp_assign_l2 returns for that hn;
+ *                dim 64 / 128 with >= 256 centroids narrow the search with two MFMA passes and re-check the near-ties with the
+ *                chain, and a chunk whose candidate list overflows goes through the exact kernel: the labels are the same)
+ *   s[t]       = that maximal value;  x2[t] = chain of x_t[d]^2
+ *   sqdist[t]  = fl32(x2[t] - 2 s[t])                                                   (2 s is exact: the reference's
+ *                x^2 + y^2 - 2xy with the rounding points pinned; a few ulps below zero for a token that equals a centroid)
+ *   row t is an outlier iff sqdist[t] > threshold_sq, a strict fp32 compare.
+ * out_rows (capacity n_tokens) receives the outlier rows in ascending order, *out_count how many; out_sqdist / out_nearest
+ * [n_tokens] are optional.  The compaction is ordered (per-tile counts -> scan -> write): nothing depends on scheduling, and
+ * there is no float atomic.  n_tokens == 0 succeeds with *out_count = 0.
+ * Errors: FP_EINVAL for n_centroids < 1, a negative size, a NaN or negative threshold_sq, a centroid or embedding value that is
+ * not finite (checked on the device); FP_EUNSUPPORTED for dim outside [1, 256]; FP_ENOMEM / FP_EHIP from the runtime. */
+int fp_centroid_outliers(int device_id, const uint16_t* centroids_f16 /*[n_centroids, dim]*/, int64_t n_centroids, int32_t dim,
+                         const uint16_t* embeddings_f16 /*[n_tokens, dim]*/, int64_t n_tokens, float threshold_sq,
+                         int64_t* out_rows /*[n_tokens] capacity*/, int64_t* out_count, float* out_sqdist /*[n_tokens] or NULL*/,
+                         int64_t* out_nearest /*[n_tokens] or NULL*/);
+/* Of the calling thread's last fp_centroid_outliers call: out[0..2] = chunks processed, chunks that took the MFMA narrowing, and
+ * those of them sent on to the exact kernel; out[3..6] = device microseconds (HIP events, summed over the chunks) of upload + data
+ * check, assignment, distance + compaction, download.  Returns 1 when that call succeeded, else 0 (the figures are stale). */
+int fp_centroid_outliers_last_counts(int64_t* out, int cap);
+
 /* ---- `reconstruct_embeddings` (rust/utils/embeddings.rs:12-69) ----------------------- */
 /* Decompresses whole documents to fp32 rows. out: host [sum(len(doc)) , dim] f32 in the
  * order of doc_ids (ids may repeat); out_lengths [n]. `out_capacity_rows` guards the buffer: when it is too small the call fails
