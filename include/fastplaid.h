@@ -124,14 +124,25 @@ int32_t fp_index_tickets_ok(const fp_index* index);
  * reference's summation order (their scores are then the reference's bit for bit), the others keep the MFMA score.
  * FP_MAXSIM_REPAIR=2 in the environment re-evaluates every flagged document: every returned score is then the reference's.
  *
- * This rests on two CERTIFICATION WINDOWS that are empirical margins, not worst-case bounds.  An fp32 MFMA result is taken as
- * "the reference's ascending fp32 chain rounds to the same fp16 value" when it lies further from every fp16 rounding boundary
- * than w0 |q| c_max + kappa |x| (centroid scores: w0 = 2^-21.5, kappa = 2^-20) resp. 2^-19 |q_col| (MaxSim column maxima); the
- * worst-case reordering error of a D-term fp32 sum, D 2^-24 sum |a_k b_k|, is ~2^-17 at D = 128 and would flag far more.
- * Measured: 0 unflagged differences in 12.9 G centroid scores and 12.8 M column maxima, the first unflagged difference appears
- * at a QUARTER of the shipped centroid window (profiles/r04_s1_window_sweep.txt, r04_cert_stats.jsonl).  So "identical ids"
- * holds with overwhelming probability on data like the tested corpora, not by construction; an adversarially built input is
- * not covered.  FP_TEST=s1_w0_log2=..,s1_kappa_log2=.. widen the centroid window (cost: more entries re-evaluated).
+ * This rests on two CERTIFICATION WINDOWS.  An fp32 MFMA result is taken as "the reference's ascending fp32 chain rounds to
+ * the same fp16 value" when it lies further from every fp16 rounding boundary than w0 |q| c_max + kappa |x| (centroid scores)
+ * resp. 2^-19 |q_col| (MaxSim column maxima); the worst-case reordering error of a D-term fp32 sum, D 2^-24 sum |a_k b_k|, is
+ * ~2^-17 at D = 128 and would flag far more.
+ *   Covered by construction: chains whose products all have ONE sign and comparable size (a query token that matches a
+ * centroid -- the highest scores, which the probe and the approximate stage depend on).  kappa = (D/2 + D/16) 2^-24 =
+ * 2^-17.83 at D = 128 (x dim / 128 above) is the sum of the chain's D - 1 half-ulp roundings of partial sums that grow
+ * linearly to |x|, plus the MFMA's own block roundings.  Until tests/golden/rounding existed kappa was 2^-20: two-amplitude
+ * sign vectors (what a 1-bit or 2-level encoder emits) reached 1.76 x that window and gave centroid scores one fp16 ulp off the
+ * reference's, unflagged, on the device (profiles/r12_rounding_boundaries.txt).  Also covered: sums that are exact in fp32
+ * (values on a coarse grid), on, next to and far from fp16 midpoints, subnormals and zeros.
+ *   Still empirical margins: w0 = 2^-21.5 (the part of the window that does not shrink with |x|: chains WITH cancellation, whose
+ * partial sums exceed |x|), the MaxSim window 2^-19 |q_col| (the constructed self-match search found no column that escapes it)
+ * and same-sign chains whose large products all come first (bound 2^-17 |x|).  Measured on random data: 0 unflagged
+ * differences in 12.9 G centroid scores and 12.8 M column maxima; with BOTH terms shrunk together the first unflagged difference
+ * appeared at a QUARTER of the window of that time, w0 = 2^-23.5 with kappa = 2^-22 (profiles/r04_s1_window_sweep.txt,
+ * r04_cert_stats.jsonl).  So for such chains "identical ids" holds with overwhelming
+ * probability on data like the tested corpora, not by construction; an adversarially built cancellation is not covered.
+ * FP_TEST=s1_w0_log2=..,s1_kappa_log2=.. move the centroid window (cost: more entries re-evaluated).
  */
 int fp_search(const fp_index* index, const uint16_t* queries, int32_t n_queries, int32_t q_len, int32_t dim,
               const fp_search_params* params, const int64_t* subset_ids, const int64_t* subset_offsets,

@@ -9,7 +9,9 @@ k_probe_tau / k_lz_exact) -- no GPU needed:
 h = round-to-nearest-even to fp16.  The restatement follows the device code line by line in fp32 arithmetic."""
 import numpy as np
 
-KAPPA = np.float32(2.0 ** -20)
+from s1_window_model import s1_kappa
+
+KAPPA = s1_kappa(128)   # the library's default at dim 128, from the one place the tests keep it
 
 
 def mono16(h):
