@@ -1806,8 +1806,9 @@ extern "C" int fp_search_trace(const fp_index* index, const uint16_t* query, int
 }
 
 extern "C" int fp_last_search_counts(int64_t* out, int cap) {
-  int n = std::min(cap, 6);
-  for (int i = 0; i < n; ++i) out[i] = g_last_counts[i];
+  int n = std::min(cap, 7);
+  for (int i = 0; i < n && i < 6; ++i) out[i] = g_last_counts[i];
+  if (n > 6) out[6] = fpk_approx_line_launches();
   return n;
 }
 

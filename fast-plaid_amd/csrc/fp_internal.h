@@ -282,6 +282,7 @@ void fpk_approx(const FpIndexDev& ix, const uint16_t* S, const FpSearchShape& sh
 // bound-and-refine front of S4 (see fp_kernels.hip): 8-bit bins of S, per-candidate bin sums, per-query cut, ordered survivors
 #define FP_SURV_CHUNK 2048
 #define FP_L0_CHUNK 8192   // candidates per workgroup of level 0's survivor count / compaction
+int64_t fpk_approx_line_launches();   // launches of the line-fed form (k_approx_lines) on this thread so far: fp_last_search_counts()[6]
 void fpk_approx_q8_bounds(const FpIndexDev& ix, const uint8_t* S8, const FpSearchShape& sh, const int64_t* cand_off, const int32_t* cand_pid,
                           int64_t M, uint32_t* kq, hipStream_t st);
 void fpk_approx_q8_cut(const FpSearchShape& sh, const int64_t* cand_off, const int32_t* cand_pid, int64_t M, uint32_t* q8hist, uint32_t* kq,

@@ -2351,6 +2351,10 @@ void fpk_cand_compact(const uint32_t* bitmap, const uint32_t* subbm, const int32
 // combined at the end -- a 33-code document is ONE step of row gathers instead of five dependent ones.  For the refine calls
 // of the bound stages (a few thousand documents per query: the chip is short of independent chains, not of lanes; measured at
 // cfg2, S4 refine: 0.457 ms with PPD 1, 0.397 ms with PPD 1 and sixteen times the workgroups, see fpk_approx).
+// Where the index carries one range of 128-byte code lines (level 0's, fp_synth.hip) the PPD 4 launches run k_approx_lines below
+// instead: the same lanes, maxima and sum, the codes from the document's line -- id -> line -> rows, three dependent steps where
+// this kernel has five for a document of more than 32 codes (cfg2: 133.6 -> 115.6 us per launch, profiles/r13_approx_lines.txt).
+// This kernel stays for PPD 1, for tables of several ranges, for indexes without lines and behind FP_TEST=ap_lines=0.
 // LZ (S1's lazy form, FpLazyS1): S holds upper candidates, so the sum below is an UPPER bound A_up of the approximate score.  How far
 // the reference's score can lie below it is bounded per QUERY from the column maxima (k_probe_tau: lz_tight) -- valid as long as
 // every column maximum of every scored document is non-negative, which this kernel checks on its way (negflag[b] = 1 otherwise:
@@ -2487,6 +2491,173 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   }
 }
 
+// The six 20-bit codes of one 16-byte piece of a packed code line (fp_synth.hip, "packed unique codes"; bits 120..126: how many of
+// them are real, bit 127 of a first line's last piece: the document has extra lines).  Shared by k_l0_scan and k_approx_lines.
+__device__ __forceinline__ void pcode_codes6(const uint4& pc, uint32_t (&c)[6]) {
+  c[0] = pc.x & 0xFFFFFu;
+  c[1] = __builtin_amdgcn_alignbit(pc.y, pc.x, 20) & 0xFFFFFu;
+  c[2] = (pc.y >> 8) & 0xFFFFFu;
+  c[3] = __builtin_amdgcn_alignbit(pc.z, pc.y, 28) & 0xFFFFFu;
+  c[4] = __builtin_amdgcn_alignbit(pc.w, pc.z, 16) & 0xFFFFFu;
+  c[5] = (pc.w >> 4) & 0xFFFFFu;
+}
+
+// k_approx<4, LZ> FED FROM THE PACKED CODE LINES (indexes with one range of 128-byte lines: fpk_approx).  The chain of the kernel
+// above is  id -> uoff -> ucodes -> rows -> rows again for the codes 32.. ; level 0 already keeps a document's distinct codes as
+// ONE aligned 128-byte line at line <document id> (k_l0_scan), so here it is  id -> line -> rows:  one request for the codes
+// instead of ~3 (two offsets, ~133 unaligned bytes) and all 48 codes of a line in ONE step of row gathers.
+//   * 16 lanes per candidate as above; quad p owns the pieces p and p + 4 (codes 6p .. 6p+5 and 24+6p .. 24+6p+5: the typical
+//     33-code document spreads over all four quads, 12 / 9 / 6 / 6 gathers per lane); each lane loads its quad's two pieces itself
+//     (the four lanes of a quad share the address, the 16 lanes of a candidate one line).
+//   * slots past a piece's count hold the scan's pad code -- the index of a zero byte behind ITS table, NOT a row of S: in the
+//     first piece they are replaced by the piece's first code (max is idempotent), a second piece without codes is not gathered,
+//     a quad without codes gathers nothing and contributes the mask value, as above.
+//   * a document with more than 48 codes (the flag in its first line's last piece; uniform over the candidate's lanes through a
+//     ballot) walks uoff / ucodes as the kernel above does, unpipelined: 0.15 % of the benchmark corpus.
+//   * the next candidate's line and the id after that are in flight while the rows are gathered; the codes stay in registers
+//     over the 32-column chunks.
+// Maxima over the same code sets, the same exchange and the same ascending sum: results equal k_approx<4, LZ>'s bit for bit.
+template <bool LZ>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_approx_lines(const uint16_t* __restrict__ S, int64_t C, int Q, int Qp,
+                                                const int64_t* __restrict__ cand_off, const int32_t* __restrict__ cand_pid,
+                                                const int64_t* __restrict__ uoff, const int32_t* __restrict__ ucodes,
+                                                const uint4* __restrict__ pcodes,
+                                                float* __restrict__ approx, const int32_t* __restrict__ cnt, int64_t cap,
+                                                float* __restrict__ scat, const int32_t* __restrict__ scat_idx,
+                                                const int64_t* __restrict__ scat_off, uint32_t* __restrict__ negflag) {
+  const int b = blockIdx.y;
+  const int64_t beg = cand_off ? cand_off[b] : (int64_t)b * cap;
+  const int64_t n = cnt ? (cnt[b] < cap ? (int64_t)cnt[b] : cap) : cand_off[b + 1] - beg;
+  const int64_t sbase = scat ? scat_off[b] : 0;
+  constexpr int CPB = 16;                     // candidates per block
+  const int sub = threadIdx.x & 3;            // 16-byte piece of the 64-byte row chunk
+  const int pp = (threadIdx.x >> 2) & 3;      // which quad of the candidate
+  const int cshift = threadIdx.x & 48;        // first lane of the candidate within its wave
+  const half_t negm = (half_t)NEG_MASK_F;
+  const h2 neg2 = {negm, negm};
+  const uint16_t* Sb = S + (int64_t)b * C * Qp + sub * 8;
+  const int64_t stride = (int64_t)gridDim.x * CPB;
+  const int nch = Qp / 32;
+  int64_t i = (int64_t)blockIdx.x * CPB + (threadIdx.x >> 4);
+  if (i >= n) return;
+  const int32_t* cpids = cand_pid + beg;
+  int32_t pid = cpids[i];
+  int32_t npid = i + stride < n ? cpids[i + stride] : 0;
+  uint4 pa = pcodes[(int64_t)pid * 8 + pp], pb = pcodes[(int64_t)pid * 8 + 4 + pp];
+  for (; i < n; i += stride) {
+    uint4 na = pa, nb = pb;
+    int32_t nnpid = 0;
+    if (i + stride < n) {
+      na = pcodes[(int64_t)npid * 8 + pp];
+      nb = pcodes[(int64_t)npid * 8 + 4 + pp];
+      if (i + 2 * stride < n) nnpid = cpids[i + 2 * stride];
+    }
+    uint32_t ca[6], cb[6];
+    pcode_codes6(pa, ca);
+    pcode_codes6(pb, cb);
+    const int cna = (int)((pa.w >> 24) & 0x7Fu), cnb = (int)((pb.w >> 24) & 0x7Fu);
+#pragma unroll
+    for (int k = 1; k < 6; ++k) {
+      ca[k] = k < cna ? ca[k] : ca[0];
+      cb[k] = k < cnb ? cb[k] : cb[0];
+    }
+    // (the candidate's lanes run the same trip counts, so all 16 are active here)
+    const bool xlines = ((__ballot((pb.w >> 31) != 0u) >> cshift) & 0xFFFFull) != 0ull;
+    int64_t u0 = 0;
+    int len = 0;
+    if (xlines) {
+      u0 = uoff[pid];
+      len = (int)(uoff[pid + 1] - u0);
+    }
+    float total = 0.f;
+    for (int ch = 0; ch < nch; ++ch) {
+      h2 m0 = neg2, m1 = neg2, m2 = neg2, m3 = neg2;
+      const uint16_t* Sc = Sb + ch * 32;
+      if (!xlines) {
+        if (cna > 0) {
+          uint4 v[6];
+#pragma unroll
+          for (int k = 0; k < 6; ++k) v[k] = *reinterpret_cast<const uint4*>(Sc + (int64_t)ca[k] * Qp);
+          if (cnb > 0) {   // (the second piece's rows are in flight with the first's: loads return in order)
+            uint4 w[6];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) w[k] = *reinterpret_cast<const uint4*>(Sc + (int64_t)cb[k] * Qp);
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+              m0 = pk_max(m0, u32_as_h2(w[k].x));
+              m1 = pk_max(m1, u32_as_h2(w[k].y));
+              m2 = pk_max(m2, u32_as_h2(w[k].z));
+              m3 = pk_max(m3, u32_as_h2(w[k].w));
+            }
+          }
+#pragma unroll
+          for (int k = 0; k < 6; ++k) {
+            m0 = pk_max(m0, u32_as_h2(v[k].x));
+            m1 = pk_max(m1, u32_as_h2(v[k].y));
+            m2 = pk_max(m2, u32_as_h2(v[k].z));
+            m3 = pk_max(m3, u32_as_h2(v[k].w));
+          }
+        }
+      } else {
+        const int32_t* cp = ucodes + u0;
+        for (int t = 8 * pp; t < len; t += 32) {
+          int32_t code[8];
+          uint4 v[8];
+#pragma unroll
+          for (int k = 0; k < 8; ++k) code[k] = cp[(t + k < len) ? t + k : (len - 1)];
+#pragma unroll
+          for (int k = 0; k < 8; ++k) v[k] = *reinterpret_cast<const uint4*>(Sc + (int64_t)code[k] * Qp);
+#pragma unroll
+          for (int k = 0; k < 8; ++k) {
+            m0 = pk_max(m0, u32_as_h2(v[k].x));
+            m1 = pk_max(m1, u32_as_h2(v[k].y));
+            m2 = pk_max(m2, u32_as_h2(v[k].z));
+            m3 = pk_max(m3, u32_as_h2(v[k].w));
+          }
+        }
+      }
+#pragma unroll
+      for (int x = 4; x < 16; x <<= 1) {
+        m0 = pk_max(m0, u32_as_h2((uint32_t)__shfl_xor((int)h2_as_u32(m0), x, 64)));
+        m1 = pk_max(m1, u32_as_h2((uint32_t)__shfl_xor((int)h2_as_u32(m1), x, 64)));
+        m2 = pk_max(m2, u32_as_h2((uint32_t)__shfl_xor((int)h2_as_u32(m2), x, 64)));
+        m3 = pk_max(m3, u32_as_h2((uint32_t)__shfl_xor((int)h2_as_u32(m3), x, 64)));
+      }
+      // (the ascending fp32 column sum of k_approx)
+      const int q0 = ch * 32 + sub * 8;
+      const float c0 = (q0 + 0 < Q) ? (float)m0.x : 0.f, c1 = (q0 + 1 < Q) ? (float)m0.y : 0.f;
+      const float c2 = (q0 + 2 < Q) ? (float)m1.x : 0.f, c3 = (q0 + 3 < Q) ? (float)m1.y : 0.f;
+      const float c4 = (q0 + 4 < Q) ? (float)m2.x : 0.f, c5 = (q0 + 5 < Q) ? (float)m2.y : 0.f;
+      const float c6 = (q0 + 6 < Q) ? (float)m3.x : 0.f, c7 = (q0 + 7 < Q) ? (float)m3.y : 0.f;
+#define AP_LANE_STEP(CTRL)                                                                                     \
+      {                                                                                                            \
+        float r = total;                                                                                           \
+        r += c0; r += c1; r += c2; r += c3; r += c4; r += c5; r += c6; r += c7;                                    \
+        total = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(r), CTRL, 0xF, 0xF, false));               \
+      }
+      AP_LANE_STEP(0x00)
+      AP_LANE_STEP(0x55)
+      AP_LANE_STEP(0xAA)
+      AP_LANE_STEP(0xFF)
+#undef AP_LANE_STEP
+      if constexpr (LZ) {
+        if ((h2_as_u32(m0) | h2_as_u32(m1) | h2_as_u32(m2) | h2_as_u32(m3)) & 0x80008000u) negflag[b] = 1u;
+      }
+    }
+    if (sub == 0 && pp == 0) {
+      if (approx) approx[beg + i] = total;
+      if (scat) scat[sbase + scat_idx[beg + i]] = total;
+    }
+    pid = npid;
+    npid = nnpid;
+    pa = na;
+    pb = nb;
+  }
+}
+
+static thread_local int64_t g_ap_line_launches = 0;
+int64_t fpk_approx_line_launches() { return g_ap_line_launches; }
+
 void fpk_approx(const FpIndexDev& ix, const uint16_t* S, const FpSearchShape& sh, const int64_t* cand_off,
                 const int32_t* cand_pid, int64_t M, float* approx, hipStream_t st, const int32_t* cnt, int64_t cap, float* scat,
                 const int32_t* scat_idx, const int64_t* scat_off, const FpLazyS1* lz) {
@@ -2504,6 +2675,19 @@ void fpk_approx(const FpIndexDev& ix, const uint16_t* S, const FpSearchShape& sh
   // (an XCD-affine query assignment was measured slower when every candidate is scored: 8.3 vs 7.6 ms, round 1; and makes no
   // difference for the refine calls of the bound stages, ~6000 documents per query: 0.445 ms either way, round 3 -- their
   // ~200 k row gathers per query hardly repeat a row, FETCH_SIZE equals the logical bytes)
+  // The wide launches read the codes from the packed lines where the index has them as one range of 128-byte lines
+  // (k_approx_lines; FP_TEST=ap_lines=0: the kernel above everywhere, for A/B runs and the parity test).
+  static const bool ap_lines = fp_test_opt("ap_lines", 1) != 0;
+  if (wide && ap_lines && ix.pcodes != nullptr && ix.n_ranges == 1 && ix.l0_ppl == 8) {
+    ++g_ap_line_launches;
+    if (lz)
+      hipLaunchKernelGGL((k_approx_lines<true>), dim3((unsigned)bx, (unsigned)sh.B), dim3(256), 0, st, S, ix.C, sh.Q, sh.Qp, cand_off, cand_pid,
+                         ix.uoff, ix.ucodes, ix.pcodes, approx, cnt, cap, scat, scat_idx, scat_off, lz->negflag);
+    else
+      hipLaunchKernelGGL((k_approx_lines<false>), dim3((unsigned)bx, (unsigned)sh.B), dim3(256), 0, st, S, ix.C, sh.Q, sh.Qp, cand_off, cand_pid,
+                         ix.uoff, ix.ucodes, ix.pcodes, approx, cnt, cap, scat, scat_idx, scat_off, (uint32_t*)nullptr);
+    return;
+  }
   if (lz) {
     if (wide)
       hipLaunchKernelGGL((k_approx<4, true>), dim3((unsigned)bx, (unsigned)sh.B), dim3(256), 0, st, S, ix.C, sh.Q, sh.Qp, cand_off, cand_pid,
@@ -3205,14 +3389,7 @@ __global__ __launch_bounds__(1024) void k_l0_scan(const uint8_t* __restrict__ e8
   // piece's count repeat its last code (fp_synth.hip): all six are summed and (6 - count) x the last taken off again (an empty
   // piece: 6 x code 0 - 6 x code 0).  Bit 24 of the result flags an escape / infinite code (v >= 240) among the real ones.
   // The table sits at LDS address 0 (checked at kernel entry), so a code IS its ds_read address.
-  auto codes6 = [](const uint4& pc, uint32_t (&c)[6]) {
-    c[0] = pc.x & 0xFFFFFu;
-    c[1] = __builtin_amdgcn_alignbit(pc.y, pc.x, 20) & 0xFFFFFu;
-    c[2] = (pc.y >> 8) & 0xFFFFFu;
-    c[3] = __builtin_amdgcn_alignbit(pc.z, pc.y, 28) & 0xFFFFFu;
-    c[4] = __builtin_amdgcn_alignbit(pc.w, pc.z, 16) & 0xFFFFFu;
-    c[5] = (pc.w >> 4) & 0xFFFFFu;
-  };
+  auto codes6 = [](const uint4& pc, uint32_t (&c)[6]) { pcode_codes6(pc, c); };   // (shared with k_approx_lines)
   auto piece = [&](const uint4& pc) -> uint32_t {
     // (slots past the piece's count point at a zero byte behind the table slice: all six are summed as they are; bit 31 of the
     // word: "the document has extra lines", first line's last piece only)

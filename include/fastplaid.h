@@ -205,7 +205,8 @@ uint64_t fp_graph_replay_count(void);
  * reference's summation order (exact-order repair), out[3] = sub-batches, out[4] = the form of S4 the last sub-batch ran
  * (0 every candidate scored exactly, 1 8-bit bound stage, 2 level 0, 3 level 0 over the hot codes; -1 when the call was a graph
  * replay), out[5] = lazy-S1 list overflows the scratch that served the call remembers (>= 2: S1's lazy form is off for it, to
- * be tried again after 256 batches).  Returns entries written (cap >= 6 for all). */
+ * be tried again after 256 batches), out[6] (cap >= 7) = launches, on this thread since the process started, of S4's exact kernel in
+ * its form fed from the packed code lines (a running total: take differences; a graph replay adds none).  Returns entries written. */
 int fp_last_search_counts(int64_t* out, int cap);
 
 /* Centroid scores (S1, search.rs:491).  Every fp32 MFMA result x is certified against the fp16 rounding boundaries with the
