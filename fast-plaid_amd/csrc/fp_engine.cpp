@@ -311,6 +311,9 @@ static thread_local uint64_t g_last_s1[4];   // FP_S1_STATS: S1's certification 
 static bool s1_stats_enabled() { static const bool on = getenv("FP_S1_STATS") != nullptr; return on; }
 // FP_MAXSIM_REPAIR: 0 off, 1 (default) the near-tied documents, 2 every flagged document
 static int maxsim_repair_mode() { static const int v = [] { const char* e = getenv("FP_MAXSIM_REPAIR"); return e ? atoi(e) : 1; }(); return v; }
+// the shapes of the K-sliced kernel were served by exact chains before it and returned the reference's scores bit for bit
+// (tools/s1_exact_lab.py compares them so); they keep that: k_final_mark also marks every emitted document with a flagged column
+static bool maxsim_emit_exact(const FpIndexDev& D) { return !fpk_maxsim_fixed_shape(D.dim, D.nbits); }
 static thread_local int64_t g_last_counts[6];  // candidates, exact-scored docs, repaired docs, sub-batches, form of S4 (0 exact / 1 8-bit bounds / 2 level 0; -1: replayed graph), lazy-S1 overflows the scratch remembers (>= 2: lazy form off)
 
 // results of one (sub-)batch in one device block: ids | scores | counts
@@ -458,8 +461,8 @@ static int upload_narrow(const int64_t* host, int32_t* dev, int64_t n, hipStream
 }
 
 // residual_codec.rs:83-140 / search.rs:53-107 are generic in nbits (a divisor of 8) and dim; the centroid GEMM stages K in
-// 8-dim (16-byte) pieces, hence dim % 8.  MFMA MaxSim kernels exist for dim 48/64/96/128 x nbits 2/4; every other shape runs
-// the generic (exact, slower) MaxSim kernel.
+// 8-dim (16-byte) pieces, hence dim % 8.  Every accepted shape has an MFMA MaxSim kernel: fixed-dim ones for thirteen shapes
+// (k_maxsim6 / k_maxsim5), the K-sliced k_maxsim_sl at a runtime dim for the rest.
 static int check_shape(int nbits, int dim) {
   if (!(nbits == 1 || nbits == 2 || nbits == 4 || nbits == 8)) return fail(FP_EINVAL, "nbits must divide 8 (1, 2, 4 or 8)");
   if (dim < 8 || dim % 8 != 0 || dim > 1024) return fail(FP_EUNSUPPORTED, "dim must be a multiple of 8 in [8, 1024]");
@@ -1306,7 +1309,7 @@ static int run_maxsim(fp_index* ix, Scratch* s, const FpSearchShape& sh, int64_t
     }
     const bool marked = mode == 1 && maxsim_repair_mode() != 2 &&
                         fpk_final_mark(s->exact.as<float>(), aux.unc, aux.uncm, s->sel_cnt.as<int32_t>(), R, B, top_k, s->ms_marks.as<int32_t>(),
-                                       s->ms_nmark.as<int32_t>(), st, flat_n, flat_n ? s->ms_flat.p : nullptr) == 0;
+                                       s->ms_nmark.as<int32_t>(), st, flat_n, flat_n ? s->ms_flat.p : nullptr, maxsim_emit_exact(D)) == 0;
     s->ms_have_marks = false;
     s->ms_marked_now = marked;
     if (marked && !s->fold_stats && (size_t)B * 4 + 64 <= 4096) {   // marked documents per query -> pinned memory, summed for fp_last_search_counts after the final sync
@@ -2533,7 +2536,7 @@ static int shard_mark_and_repair(fp_index* ix, Scratch* s, const FpSearchShape& 
   s->sh_marks_mode = 0;   // 0 nothing to exchange, 1 near-tied documents (marks), 2 every flagged document
   if (maxsim_repair_mode() != 0) {
     s->sh_marks_mode = (maxsim_repair_mode() != 2 && fpk_final_mark(u_score, u_unc, u_uncm, s->u_cnt.as<int32_t>(), R, B, K, s->ms_marks.as<int32_t>(),
-                                                          s->ms_nmark.as<int32_t>(), st) == 0) ? 1 : 2;
+                                                          s->ms_nmark.as<int32_t>(), st, nullptr, nullptr, maxsim_emit_exact(ix->d)) == 0) ? 1 : 2;
     const int32_t* marks = s->sh_marks_mode == 1 ? s->ms_marks.as<int32_t>() : nullptr;
     fpk_shard_local_marks(marks, s->ms_nmark.as<int32_t>(), u_unc, s->u_cnt.as<int32_t>(), u_src, B, R, rank, s->sh_lmarks.as<int32_t>(),
                           s->sh_lnmark.as<int32_t>(), st);

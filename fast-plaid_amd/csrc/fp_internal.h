@@ -364,6 +364,7 @@ struct FpMaxsimAux {
   float* uncm;       // [B][Rcap]     the part of `unc` by which the reference's score may be lower (it may be higher by unc - uncm)
 };
 bool fpk_maxsim_fast_shape(int dim, int nbits);
+bool fpk_maxsim_fixed_shape(int dim, int nbits);   // shapes of the fixed-dim kernels (k_maxsim6 / k_maxsim5); the rest take k_maxsim_sl
 bool fpk_maxsim6_shape(int dim, int nbits);   // shapes k_maxsim6 is instantiated for
 // rows [t0, t0 + n) of ix.residuals rewritten in k_maxsim6's unit order through tmp (n * pr bytes)
 void fpk_resid_native(const FpIndexDev& ix, int64_t t0, int64_t n, uint8_t* tmp, hipStream_t st);
@@ -377,7 +378,8 @@ int fpk_maxsim(const FpIndexDev& ix, const uint16_t* q_pad, const FpSearchShape&
 // flagged documents that are near-tied in the final ranking -> marks [B][stride], nmark [B]; -1 when stride is too large for LDS
 int fpk_final_mark(const float* score, const float* unc, const float* uncm /*nullable: symmetric*/, const int32_t* cnt, int64_t stride, int B,
                    int64_t top_k, int32_t* marks, int32_t* nmark,
-                   hipStream_t st, uint32_t* flat_n = nullptr /*a zeroed counter ...*/, void* flat = nullptr /*... and the batch-wide {query, slot} list [B * stride] it counts*/);
+                   hipStream_t st, uint32_t* flat_n = nullptr /*a zeroed counter ...*/, void* flat = nullptr /*... and the batch-wide {query, slot} list [B * stride] it counts*/,
+                   bool emit_exact = false /*also mark every emitted document that has a flagged column (the shapes of k_maxsim_sl)*/);
 // exact (ascending-k) re-evaluation of the flagged columns of the marked documents (marks == nullptr: of every flagged document)
 void fpk_maxsim_repair(const FpIndexDev& ix, const uint16_t* q_pad, const FpSearchShape& sh, const int32_t* sel_pid, const int32_t* sel_cnt,
                        int64_t Rcap, const int32_t* marks, const int32_t* nmark, float* exact, const FpMaxsimAux& aux, hipStream_t st,

@@ -641,6 +641,94 @@ struct Ms6Step {   // one 16-token step of one document; wave-uniform
   int valid;
 };
 
+// an empty document (as in k_maxsim6): every column keeps the masked value, nothing to flag
+template <int NCH>
+__device__ __forceinline__ void ms6_emit_empty(const MsArgs& a, int b, int rr, int nq, int nflag, int lane, float* outp) {
+  const half_t negm = (half_t)NEG_MASK_F;
+  if (lane == 0) {
+    const float v = (float)nq * NEG_MASK_F;
+    outp[rr] = a.accumulate ? (outp[rr] + v) : v;
+    if (a.unc && !a.accumulate) { a.unc[(int64_t)b * a.Rcap + rr] = 0.f; a.uncm[(int64_t)b * a.Rcap + rr] = 0.f; }
+  }
+  if (a.cm16 && lane < 32) {
+#pragma unroll
+    for (int c = 0; c < NCH; ++c)
+      if ((a.ch_begin + c) * 32 < a.Qp) a.cm16[((int64_t)b * a.Rcap + rr) * a.Qp + (a.ch_begin + c) * 32 + lane] = __builtin_bit_cast(uint16_t, negm);
+  }
+  if (a.flags && lane == 0) {
+#pragma unroll
+    for (int c = 0; c < NCH; ++c)
+      if (a.ch_begin + c < nflag) a.flags[((int64_t)b * a.Rcap + rr) * nflag + a.ch_begin + c] = 0u;
+  }
+}
+
+// The last step of a document, k_maxsim6's epilogue as a function (k_maxsim6 keeps its inline copy -- the block under "the
+// document's last step" in its compute lambda: moving it into a call changed that kernel's generated code; k_maxsim_sl uses this
+// one).  TWO COPIES of the certification: a change to either goes into both; they differ in the order of the column sum only.  Combine the four row groups of the fp32 column maxima, round once,
+// certify, write cm16 / flags, sum the columns and add the document's score and budgets.  mx is reset for the next document.
+template <int NCH>
+__device__ __forceinline__ void ms6_finish_doc(const MsArgs& a, int b, int r, float (&mx)[NCH * 2], const float* qn, int lane, int nflag, float* outp) {
+  constexpr int NC16 = NCH * 2;
+  float total = a.accumulate ? outp[r] : 0.f, ubud = 0.f, ubm = 0.f;   // (outp[r]: a uniform address)
+  const unsigned long long upper16 = 0xFFFF0000FFFF0000ull;   // lanes with (lane & 16)
+#pragma unroll
+  for (int c = 0; c < NC16; ++c) {
+    {  // maximum over lanes l, l^16, l^32, l^48 (the same column, other row groups)
+      auto s16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(mx[c]), __float_as_uint(mx[c]), false, false);
+      float m = __builtin_fmaxf(__uint_as_float(s16[0]), __uint_as_float(s16[1]));
+      auto s32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
+      mx[c] = __builtin_fmaxf(__uint_as_float(s32[0]), __uint_as_float(s32[1]));
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    // lane l < 32 takes column 32 c + l: lanes 0-15 from group 2c, lanes 16-31 from group 2c + 1 (every row group holds both)
+    float am;   // (a plain ?: over two array elements becomes an indexed scratch access; spell the select)
+    asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(am) : "v"(mx[2 * c]), "v"(mx[2 * c + 1]), "s"(upper16));
+    const int q = (a.ch_begin + c) * 32 + (lane & 31);
+    const bool mine = (lane < 32) && (q < a.Q);
+    const half_t hm = (half_t)am;
+    float sv = mine ? (float)hm : 0.f;
+    uint32_t ef = (__float_as_uint(am) >> 23) & 0xFFu;
+    ef = ef < 113u ? 113u : ef;
+    const float halfulp = __uint_as_float((ef - 11u) << 23);
+    const float dist = halfulp - __builtin_fabsf(am - (float)hm);
+    const bool flag = mine && !(dist > qn[c * 32 + (lane & 31)]);
+    float fu = flag ? 2.0f * halfulp : 0.f;
+    float fm = (flag && !(am > (float)hm)) ? 2.0f * halfulp : 0.f;
+    if (flag && !(am < (float)hm) && !(am > (float)hm)) fu += 2.0f * halfulp;
+    const unsigned long long bal = __ballot(flag);
+    // (the one difference from k_maxsim6's copy) the columns are summed one after the other in ascending order, continuing the
+    // previous launch's sum: the reference's order.  The xor tree gives the same bits only while every partial sum is exact, which
+    // the column maxima of these shapes do not promise (dim 40, q_len 50: a maximum of -1.8e-4 next to a sum of 25.7).
+#pragma unroll
+    for (int l = 0; l < 32; ++l) total += __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(sv), l));
+    if (bal) {
+#pragma unroll
+      for (int sft = 32; sft > 0; sft >>= 1) {
+        fu += __shfl_xor(fu, sft, 64);
+        fm += __shfl_xor(fm, sft, 64);
+      }
+    }
+    ubud += fu;
+    ubm += fm;
+    if (a.cm16 && lane < 32 && (a.ch_begin + c) * 32 < a.Qp)
+      a.cm16[((int64_t)b * a.Rcap + r) * a.Qp + (a.ch_begin + c) * 32 + lane] = __builtin_bit_cast(uint16_t, hm);
+    if (a.flags && lane == 0 && a.ch_begin + c < nflag) a.flags[((int64_t)b * a.Rcap + r) * nflag + a.ch_begin + c] = (uint32_t)bal;
+  }
+  if (lane == 0) {
+    outp[r] = total;
+    if (a.unc) {
+      float* up = a.unc + (int64_t)b * a.Rcap + r;
+      *up = a.accumulate ? (*up + ubud) : ubud;
+      float* um = a.uncm + (int64_t)b * a.Rcap + r;
+      *um = a.accumulate ? (*um + ubm) : ubm;
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < NC16; ++c) mx[c] = NEG_MASK_F;
+}
+
 // waves per workgroup (one workgroup per CU): 16 where three steps of loads fit 128 registers, fewer for wide rows / two column chunks
 static constexpr int ms6_waves(int ks4, int nch, int nbits = 4) { return ks4 >= 8 ? 8 : ((ks4 >= 4 && (nch == 2 || nbits == 8)) ? 12 : 16); }
 
@@ -846,6 +934,8 @@ __global__ __launch_bounds__(ms6_waves(KS4, NCH, NBITS) * 64) __attribute__((amd
         }
         mx[c] = max3_raw(v2, v3, max3_raw(v0, v1, mx[c]));
       }
+      // (ms6_finish_doc above is this block as a function, for k_maxsim_sl: keep the two in step; likewise ms6_emit_empty and the
+      // empty-document loop further up)
       if (st.t0 + 16 >= st.len) {   // the document's last step: combine the four row groups, round, certify, sum
         float total = 0.f, ubud = 0.f, ubm = 0.f;
         const unsigned long long upper16 = 0xFFFF0000FFFF0000ull;   // lanes with (lane & 16)
@@ -945,6 +1035,299 @@ __global__ __launch_bounds__(ms6_waves(KS4, NCH, NBITS) * 64) __attribute__((amd
   }
 }
 
+// ======================================================================================================================
+// k_maxsim_sl -- k_maxsim6's operand layout at a RUNTIME dim, the contraction walked in K-slices: every (dim, nbits) the index
+// accepts that k_maxsim6 / k_maxsim5 are not instantiated for (any dim % 8 == 0 up to 1024).
+//
+// k_maxsim6 keeps a token's whole row in registers (KS4 * 4 half2 per lane and step, three steps in flight), which ends at dim
+// 256.  Here a lane holds ONE SLICE of its token at a time: 4 k-steps = 128 dims of the row, i.e. the lane's four 8-dim units
+// u = 4 s + g (s the k-step, g = lane / 16) as 16 half2 registers plus the units' residual bytes.  The fp32 accumulators of the
+// step's 16 tokens persist across the slices, so the MFMA order is ascending k over the whole row, whatever the dim.
+//   * dim % 8 == 0 only: unit u >= dim / 8 does not exist.  Its lane re-reads the row's last unit (the load count stays uniform,
+//     nothing is read past the row), the decoded registers are zeroed before the MFMA, and the query fragment of an absent unit
+//     is zero as well: zero products add nothing to an fp32 sum.  k-steps beyond ceil(dim / 32) are skipped (wave-uniform).
+//   * residual rows stay in the reference's byte order: a lane reads its unit's NBITS bytes, the four lanes of a token 4 * NBITS
+//     contiguous bytes per k-step.  The centroid row (2 B per dim against NBITS / 8) decides the access pattern: one dwordx4 per
+//     lane and k-step, 64 contiguous bytes per token, as in k_maxsim6.
+//   * normalisation: the compensated quotient norm_pair2 from the stored fp16 norm (no reciprocals for these shapes).
+//   * pipeline: the stream of (step, slice) items runs through a ring of three slice buffers -- item k is decoded and multiplied
+//     while the loads of items k+1 and k+2 (the step's next slices, or the next step's first ones) are in flight, and the codes
+//     / norms are fetched two STEPS ahead so that no row load waits for its address.  Depth two: a slice is 16 + NBITS (nbits 8)
+//     registers, three buffers are 60 - 72 of the 168 a lane has at 12 waves; next to 16 accumulators (two column chunks), the
+//     four B fragments of a k-step and norm_pair2's six temporaries the two-chunk kernels already stand at 157 - 160, so a
+//     fourth buffer would spill.  Two slices of 12 waves are 12 x 2 x 64 x (64 + 4 NBITS) B = 102 - 144 KiB of loads outstanding per CU.
+// Everything downstream of the accumulators is k_maxsim6's, as the functions ms6_finish_doc / ms6_emit_empty.
+// Resource usage: see MSSL_WAVES below.  k_maxsim_repair_sl<1 / 2 / 4 / 8>: 109 / 106 / 106 / 111 VGPRs, 4 / 2 / 1 / 0.5 KiB LDS.
+template <int NBITS>
+struct MsSlCfg {
+  static constexpr int PB = 8 / NBITS;
+  static constexpr int EW = PB >= 2 ? PB / 2 : 1;
+  static constexpr int COPIES = 64 / EW;
+  static constexpr int RW = NBITS;                    // residual words per lane and slice: 4 units x NBITS bytes
+  static constexpr int RL = NBITS >= 4 ? NBITS : 4;   // ... as loaded: nbits 1 / 2 fetch a byte / a short per k-step into a register each
+};
+template <int NBITS>
+struct MsSlBuf {
+  uint32_t e[16];                      // centroid half2 pairs of the lane's four units, k-step major (decoded in place)
+  uint32_t rl[MsSlCfg<NBITS>::RL];     // the units' residual bytes
+};
+struct MsSlItem {   // one slice of one step
+  Ms6Step st;
+  int sl;           // slice of the row (wave-uniform)
+  int32_t code;     // the lane's token: centroid id and fp16 norm
+  uint32_t nrm;
+};
+
+// Waves per workgroup (one workgroup per CU): 12 = three per SIMD = a budget of 168 registers, the same for every instantiation.
+// Compiler's resource remarks, <NBITS, NCH> = <1,1> <2,1> <4,1> <8,1>: 143 / 144 / 144 / 146 VGPRs, <1,2> <2,2> <4,2> <8,2>:
+// 160 / 157 / 157 / 160; 106 SGPRs, no scratch.  (16 waves = 128 registers: the one-chunk kernels of nbits 1 / 2 / 4 spilled 14
+// registers, the two-chunk ones do not fit at all.)  LDS is dynamic: 64 KiB + 1 KiB per 16-column group and k-step + the windows.
+#define MSSL_WAVES 12
+
+template <int NBITS, int NCH>
+__global__ __launch_bounds__(MSSL_WAVES * 64) __attribute__((amdgpu_waves_per_eu(MSSL_WAVES / 4, MSSL_WAVES / 4))) void k_maxsim_sl(const MsArgs a, const int D) {
+  using Cf = MsSlCfg<NBITS>;
+  constexpr int WAVES = MSSL_WAVES, THREADS = WAVES * 64;
+  constexpr int NC16 = NCH * 2;
+  const int nu = D >> 3;             // 8-dim units of a row
+  const int KS = (nu + 3) >> 2;      // MFMA k-steps (the last one may hold absent units)
+  const int NSL = (KS + 3) >> 2;     // slices of at most 4 k-steps
+  const int pr = nu * NBITS;         // residual bytes per token
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  unsigned char* lut = smem;                                                         // 64 KiB
+  uint4* qs = reinterpret_cast<uint4*>(smem + MS_LUT_BYTES);                        // B fragments: [NC16][KS][64] x 16 B
+  float* qn = reinterpret_cast<float*>(smem + MS_LUT_BYTES + NC16 * KS * 64 * 16);  // [NCH * 32] certification window per column
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  const int r16 = lane & 15, g = lane >> 4;
+  ms_lds_base_is_zero(smem);
+  ms6_fill_lut<NBITS>(lut, a.lut_g, tid, THREADS);
+  const uint32_t laneoff = (uint32_t)((lane & (Cf::COPIES - 1)) * Cf::EW * 4);
+  int nq = a.Q - a.ch_begin * 32;
+  nq = nq < 0 ? 0 : (nq > NCH * 32 ? NCH * 32 : nq);
+  const int nflag = a.Qp / 32;
+
+  // this workgroup's share of the flattened (query, rerank slot) space, as in k_maxsim6
+  const long long tot = a.pref[a.B];
+  const long long lo = tot * (long long)blockIdx.x / (long long)gridDim.x;
+  const long long hi_end = tot * (long long)(blockIdx.x + 1) / (long long)gridDim.x;
+  int b = 0;
+  {
+    int l = 0, h = a.B;
+    while (h - l > 1) { const int m = (l + h) >> 1; if (a.pref[m] <= lo) l = m; else h = m; }
+    b = l;
+  }
+  for (; b < a.B && a.pref[b] < hi_end; ++b) {
+    const long long pb0 = a.pref[b], pb1 = a.pref[b + 1];
+    const int ra = (int)((lo > pb0 ? lo : pb0) - pb0);
+    const int rb = (int)((hi_end < pb1 ? hi_end : pb1) - pb0);
+    if (rb <= ra) continue;
+    __syncthreads();
+    // B fragment of (16-column group c, k-step s), lane (n, gq): q[col = 16 c + n][unit 4 s + gq], zero for an absent unit
+    for (int i = tid; i < NC16 * KS * 64; i += THREADS) {
+      const int ln = i & 63, s = (i >> 6) % KS, c = (i >> 6) / KS;
+      const int col = a.ch_begin * 32 + c * 16 + (ln & 15);
+      const int u = 4 * s + (ln >> 4);
+      uint4 v = make_uint4(0, 0, 0, 0);
+      if (col < a.Qp && u < nu) v = *reinterpret_cast<const uint4*>(a.qpad + ((int64_t)b * a.Qp + col) * D + 8 * u);
+      qs[i] = v;
+    }
+    if (tid < NCH * 32) {
+      const int col = a.ch_begin * 32 + tid;
+      float ss = 0.f;
+      if (col < a.Qp) {
+        const uint16_t* qp = a.qpad + ((int64_t)b * a.Qp + col) * D;
+        for (int k = 0; k < D; ++k) { const float x = (float)__builtin_bit_cast(half_t, qp[k]); ss = __builtin_fmaf(x, x, ss); }
+      }
+      qn[tid] = a.eps_rel * __builtin_sqrtf(ss);
+    }
+    __syncthreads();
+    const int per = (rb - ra + WAVES - 1) / WAVES;
+    const int r0 = ra + wave * per;
+    if (r0 >= rb) continue;
+    const int rend = (r0 + per < rb) ? (r0 + per) : rb;
+    const int32_t* selp = a.sel_pid + (int64_t)b * a.Rcap;
+    float* outp = a.exact + (int64_t)b * a.Rcap;
+
+    // ---- the stream of 16-token steps of documents r0 .. rend-1 (wave-uniform, metadata through the scalar cache: k_maxsim6) ----
+    typedef const __attribute__((address_space(4))) int32_t* ms_cptr_i32;
+    typedef const __attribute__((address_space(4))) int64_t* ms_cptr_i64;
+    const ms_cptr_i32 selc = (ms_cptr_i32)(uintptr_t)selp;
+    const ms_cptr_i64 doffc = (ms_cptr_i64)(uintptr_t)a.doc_off;
+    auto meta = [&](int rr, long long& o, int& l) {
+      const int32_t pid = selc[rr];
+      o = doffc[pid];
+      l = (int)(doffc[pid + 1] - o);
+    };
+    for (int rr = r0; rr < rend; ++rr) {   // empty documents first; the stream below skips them
+      long long o; int l;
+      meta(rr, o, l);
+      if (l == 0) ms6_emit_empty<NCH>(a, b, rr, nq, nflag, lane, outp);
+    }
+    int it_r = r0, it_t0 = 0, it_len = 0, n_len = 0;
+    long long it_off = 0, n_off = 0;
+    if (it_r < rend) meta(it_r, it_off, it_len);
+    if (it_r + 1 < rend) meta(it_r + 1, n_off, n_len);
+    auto next_doc = [&]() {
+      ++it_r;
+      it_off = n_off;
+      it_len = n_len;
+      it_t0 = 0;
+      if (it_r + 1 < rend) meta(it_r + 1, n_off, n_len);
+    };
+    while (it_r < rend && it_len == 0) next_doc();
+    auto next_step = [&]() -> Ms6Step {
+      Ms6Step st{it_off, it_t0, it_len, it_r, it_r < rend ? 1 : 0};
+      if (st.valid) {
+        it_t0 += 16;
+        if (it_t0 >= it_len) {
+          next_doc();
+          while (it_r < rend && it_len == 0) next_doc();
+        }
+      }
+      return st;
+    };
+    // the lane's token row (clamped into the document: rows beyond it are masked at the maximum; an exhausted stream reads row 0 of
+    // codes / norms, which exists in an index without tokens too: every index array is allocated with at least one element and 64
+    // bytes of slack, and the code read there is replaced by 0 in load_cn)
+    auto row_of = [&](const Ms6Step& st) -> long long {
+      const int tok = st.t0 + r16;
+      return st.valid ? st.off + (tok < st.len ? tok : st.len - 1) : 0;
+    };
+    auto load_cn = [&](const Ms6Step& st, int32_t& code, uint32_t& nrm) {
+      const long long row = row_of(st);
+      const int32_t cd = a.codes[row];
+      code = st.valid ? cd : 0;
+      nrm = (uint32_t)a.norms[row];
+    };
+    // ---- the stream of slices: the step being sliced (s0) and the two after it, whose codes / norms are already on their way ----
+    Ms6Step s0 = next_step(), s1 = next_step(), s2 = next_step();
+    int32_t c0, c1, c2;
+    uint32_t n0, n1, n2;
+    load_cn(s0, c0, n0);
+    load_cn(s1, c1, n1);
+    load_cn(s2, c2, n2);
+    int sl_next = 0;
+    auto next_item = [&]() -> MsSlItem {
+      MsSlItem it{s0, sl_next, c0, n0};
+      if (++sl_next == NSL) {
+        sl_next = 0;
+        s0 = s1; c0 = c1; n0 = n1;
+        s1 = s2; c1 = c2; n1 = n2;
+        s2 = next_step();
+        load_cn(s2, c2, n2);
+      }
+      return it;
+    };
+    auto load_slice = [&](MsSlBuf<NBITS>& bf, const MsSlItem& it) {
+      // (an exhausted stream keeps loading, so that every path has the same number of loads in flight: centroid row 0 for both
+      // operands -- it is at least as long as a residual row, and exists in an index without tokens)
+      const uint8_t* rp = it.st.valid ? a.resid + row_of(it.st) * (long long)pr : reinterpret_cast<const uint8_t*>(a.cent);
+      const uint16_t* cp = a.cent + (long long)it.code * D;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        int u = 16 * it.sl + 4 * j + g;
+        u = u < nu ? u : nu - 1;   // an absent unit: the row's last one again (zeroed in compute)
+        const uint4 v = *reinterpret_cast<const uint4*>(cp + 8 * u);
+        bf.e[4 * j] = v.x; bf.e[4 * j + 1] = v.y; bf.e[4 * j + 2] = v.z; bf.e[4 * j + 3] = v.w;
+        if constexpr (NBITS == 1) bf.rl[j] = rp[u];
+        else if constexpr (NBITS == 2) bf.rl[j] = *reinterpret_cast<const uint16_t*>(rp + 2 * u);
+        else if constexpr (NBITS == 4) bf.rl[j] = *reinterpret_cast<const uint32_t*>(rp + 4 * u);
+        else {
+          const uint2 w = *reinterpret_cast<const uint2*>(rp + 8 * u);
+          bf.rl[2 * j] = w.x; bf.rl[2 * j + 1] = w.y;
+        }
+      }
+    };
+
+    float mx[NC16];
+    f4v acc[NC16];
+#pragma unroll
+    for (int c = 0; c < NC16; ++c) { mx[c] = NEG_MASK_F; acc[c] = f4v{0.f, 0.f, 0.f, 0.f}; }
+
+    auto compute = [&](const MsSlItem& it, MsSlBuf<NBITS>& bf) {
+      const Ms6Step& st = it.st;
+      // the slice's residual bytes in k-step order, 4 per word: ms6_decode's addressing
+      uint32_t rw[Cf::RW];
+      if constexpr (NBITS == 1) rw[0] = bf.rl[0] | (bf.rl[1] << 8) | (bf.rl[2] << 16) | (bf.rl[3] << 24);
+      else if constexpr (NBITS == 2) { rw[0] = bf.rl[0] | (bf.rl[1] << 16); rw[1] = bf.rl[2] | (bf.rl[3] << 16); }
+      else {
+#pragma unroll
+        for (int i = 0; i < Cf::RW; ++i) rw[i] = bf.rl[i];
+      }
+      // e = h(cent + w);  e^ = h(fl32(e / n))
+      ms6_decode<NBITS, Cf::RW, 16>(laneoff, rw, bf.e);
+      float r_hi, r_lo;
+      recip2((float)__builtin_bit_cast(half_t, (uint16_t)it.nrm), r_hi, r_lo);
+#pragma unroll
+      for (int i = 0; i < 16; i += 2) norm_pair2(bf.e[i], bf.e[i + 1], r_hi, r_lo);
+      if (it.sl == 0) {
+#pragma unroll
+        for (int c = 0; c < NC16; ++c) acc[c] = f4v{0.f, 0.f, 0.f, 0.f};
+      }
+      // MFMA: D[row = token][col], this lane's rows 4 g + i; k ascending over the slices
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int s = 4 * it.sl + j;
+        if (s < KS) {
+          const bool absent = 4 * s + g >= nu;
+          const h8 av = __builtin_bit_cast(h8, make_uint4(absent ? 0u : bf.e[4 * j], absent ? 0u : bf.e[4 * j + 1], absent ? 0u : bf.e[4 * j + 2],
+                                                          absent ? 0u : bf.e[4 * j + 3]));
+#pragma unroll
+          for (int c = 0; c < NC16; ++c) {
+            const h8 bq = __builtin_bit_cast(h8, qs[(c * KS + s) * 64 + lane]);
+            acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, bq, acc[c], 0, 0, 0);
+          }
+        }
+      }
+      if (it.sl != NSL - 1) return;
+      // the step's last slice: its 16 tokens into the running column maxima
+      const bool partial = st.t0 + 16 > st.len;
+#pragma unroll
+      for (int c = 0; c < NC16; ++c) {
+        float v0 = acc[c][0], v1 = acc[c][1], v2 = acc[c][2], v3 = acc[c][3];
+        if (partial) {
+          const int rowb = st.t0 + 4 * g;
+          if (rowb + 0 >= st.len) v0 = NEG_MASK_F;
+          if (rowb + 1 >= st.len) v1 = NEG_MASK_F;
+          if (rowb + 2 >= st.len) v2 = NEG_MASK_F;
+          if (rowb + 3 >= st.len) v3 = NEG_MASK_F;
+        }
+        mx[c] = max3_raw(v2, v3, max3_raw(v0, v1, mx[c]));
+      }
+      if (st.t0 + 16 >= st.len) ms6_finish_doc<NCH>(a, b, st.r, mx, qn, lane, nflag, outp);   // the document's last step
+    };
+
+    // ---- software pipeline: item k is computed while the loads of items k+1 and k+2 are in flight.  Per iteration: codes of a
+    // further step (inside next_item, when a step has been sliced up), slice loads (k+2), compute (k): a code load is always older
+    // than the row loads issued around its first use (see k_maxsim6 for the memory clobbers) ----
+    MsSlBuf<NBITS> B0, B1, B2;
+    asm volatile("" ::: "memory");
+    MsSlItem i0 = next_item(), i1 = next_item(), i2{};
+    asm volatile("" ::: "memory");
+    load_slice(B0, i0);
+    load_slice(B1, i1);
+    asm volatile("" ::: "memory");
+    auto body = [&](MsSlBuf<NBITS>& cur, MsSlBuf<NBITS>& ld) {
+      i2 = next_item();
+      asm volatile("" ::: "memory");
+      load_slice(ld, i2);
+      asm volatile("" ::: "memory");
+      compute(i0, cur);
+      asm volatile("" ::: "memory");
+      i0 = i1; i1 = i2;
+    };
+    while (true) {
+      if (!i0.st.valid) break;
+      body(B0, B2);
+      if (!i0.st.valid) break;
+      body(B1, B0);
+      if (!i0.st.valid) break;
+      body(B2, B1);
+    }
+  }
+}
+
 // ---- any dim / nbits: exact ascending-k chains (the arithmetic of k_token_scores; bit-identical to the reference, so nothing
 // is ever flagged).  One 64-thread workgroup per (query, rerank slot); lane j owns query columns j, j+64, ...  Slower than the
 // MFMA kernel by an order of magnitude; used for the shapes the fast path is not instantiated for.
@@ -1015,6 +1398,9 @@ __global__ __launch_bounds__(64) void k_maxsim_generic(const uint16_t* __restric
 // suffix-max scan.  Flagged documents in such a conflict (with at least one of the two inside the emitted top_k) are marked;
 // every unmarked document's interval is disjoint from all others, so after the marked ones are re-scored exactly the order is
 // the reference's.  marks[b][0..nmark[b]) = rerank slots.
+// EMIT_EXACT (the shapes of k_maxsim_sl): every EMITTED document that has a flagged column is marked as well, so that each returned
+// score is the reference's bit for bit, as it was when these shapes ran the exact chains; false leaves the kernel as it was.
+template <bool EMIT_EXACT>
 __global__ __launch_bounds__(1024) void k_final_mark(const float* __restrict__ score, const float* __restrict__ unc,
                                                      const float* __restrict__ uncm /*nullable: symmetric intervals*/, const int32_t* __restrict__ cnt,
                                                      int64_t stride, int npow2, int64_t top_k, int32_t* __restrict__ marks,
@@ -1082,7 +1468,7 @@ __global__ __launch_bounds__(1024) void k_final_mark(const float* __restrict__ s
           const float lmin = i > 0 ? lo[i - 1] : inf;
           const float hmax = i + 1 < 1024 ? hi[i + 1] : -inf;
           conflict = !(si + up < lmin) || !(si - um > hmax);
-          conflict = conflict || um > 0.00095f || up > 0.00095f;   // (see the general path below)
+          conflict = conflict || um > 0.00095f || up > 0.00095f || EMIT_EXACT;   // (see the general path below)
         } else {
           conflict = !(si + up < lmin_top);
         }
@@ -1169,7 +1555,7 @@ __global__ __launch_bounds__(1024) void k_final_mark(const float* __restrict__ s
         // ... and an emitted document whose flagged columns could add up to more than the score tolerance (three or more of them
         // on one side in the top binade: rare at 32 query tokens, less so at 128) is re-evaluated too, so that EVERY returned score
         // is within 1e-3 of the reference's by construction, not by the odds
-        conflict = conflict || um > 0.00095f || up > 0.00095f;
+        conflict = conflict || um > 0.00095f || up > 0.00095f || EMIT_EXACT;
       } else {
         conflict = !(si + up < lmin_top);                         // outside the emitted range: only a jump into it matters
       }
@@ -1323,6 +1709,154 @@ __global__ __launch_bounds__(64) void k_maxsim_repair(const uint16_t* __restrict
   }
 }
 
+// k_maxsim_repair_sl: the repair at a runtime dim (the shapes of k_maxsim_sl).  Same work items, one wave each, a token per
+// lane -- but a row of up to 1024 dims does not fit a lane's registers, so it is walked in the slices of k_maxsim_sl (16 units =
+// 128 dims = 64 half2 registers, reference byte order), with one chain accumulator per flagged column carried across the
+// slices: the chain still runs over ascending k with one fp32 rounding per step.  The flagged columns of a 32-column chunk are
+// taken MSR_G at a time (the window flags 1 - 6 % of the columns: a chunk rarely has more); each group decodes the slices again.
+#define MSR_G 4
+template <int NBITS>
+__global__ __launch_bounds__(64) void k_maxsim_repair_sl(const uint16_t* __restrict__ cent, const uint16_t* __restrict__ lut_g,
+                                                         const int32_t* __restrict__ codes, const uint16_t* __restrict__ norms,
+                                                         const uint8_t* __restrict__ resid, const int64_t* __restrict__ doc_off, int D,
+                                                         const uint16_t* __restrict__ qpad, int Q, int Qp, const int32_t* __restrict__ sel_pid,
+                                                         const int32_t* __restrict__ sel_cnt, int64_t Rcap, const int32_t* __restrict__ marks,
+                                                         const int32_t* __restrict__ nmark, float* __restrict__ exact, float* __restrict__ unc,
+                                                         uint16_t* __restrict__ cm16, uint32_t* __restrict__ flags,
+                                                         const uint32_t* __restrict__ flat_n, const uint2* __restrict__ flat) {
+  constexpr int PB = 8 / NBITS;
+  __shared__ uint16_t slut[256 * PB];
+  int b = flat ? 0 : (int)blockIdx.y;
+  const int nwork = flat ? (int)*flat_n : (marks ? nmark[b] : sel_cnt[b]);
+  if ((int)blockIdx.x >= nwork) return;
+  const int lane = threadIdx.x;
+  for (int i = lane; i < 256 * PB; i += 64) slut[i] = lut_g[i];
+  __syncthreads();
+  const int nflag = Qp / 32;
+  const int nu = D >> 3, NSL = (nu + 15) >> 4, pr = nu * NBITS;
+  for (int wi = blockIdx.x; wi < nwork; wi += gridDim.x) {
+    int r;
+    if (flat) {
+      const uint2 it = flat[wi];
+      b = (int)it.x;
+      r = (int)it.y;
+    } else {
+      r = marks ? marks[(int64_t)b * Rcap + wi] : wi;
+    }
+    const int64_t slot = (int64_t)b * Rcap + r;
+    if (!(unc[slot] > 0.f)) continue;
+    const int32_t pid = sel_pid[slot];
+    const long long off = doc_off[pid];
+    const int len = (int)(doc_off[pid + 1] - off);
+    float total = 0.f;
+    for (int ch = 0; ch < nflag; ++ch) {
+      const int q = ch * 32 + (lane & 31);
+      float cv = (lane < 32 && q < Q) ? (float)__builtin_bit_cast(half_t, cm16[slot * Qp + q]) : 0.f;
+      const uint32_t fm = flags[slot * nflag + ch];
+      if (fm) {
+        float colmax = NEG_MASK_F;   // lane c: running exact maximum of column c
+        uint32_t frem = fm;
+        while (frem) {
+          int cols[MSR_G];   // this group's columns (wave-uniform), -1 = none
+#pragma unroll
+          for (int j = 0; j < MSR_G; ++j) {
+            cols[j] = frem ? __builtin_ctz(frem) : -1;
+            frem &= frem - 1;   // (0 stays 0)
+          }
+          for (int t0 = 0; t0 < len; t0 += 64) {
+            int tok = t0 + lane;
+            const bool live = tok < len;
+            tok = live ? tok : len - 1;
+            const uint16_t* cp = cent + (long long)codes[off + tok] * D;
+            const uint8_t* rp = resid + (off + tok) * (long long)pr;
+            float r_hi, r_lo;
+            recip2((float)__builtin_bit_cast(half_t, norms[off + tok]), r_hi, r_lo);
+            float acc[MSR_G];
+#pragma unroll
+            for (int j = 0; j < MSR_G; ++j) acc[j] = 0.f;
+            for (int sl = 0; sl < NSL; ++sl) {
+              const int nus = nu - 16 * sl < 16 ? nu - 16 * sl : 16;   // units of this slice
+              uint32_t e[64];
+#pragma unroll
+              for (int u = 0; u < 16; ++u) {
+                if (u < nus) {
+                  const int gu = 16 * sl + u;
+                  const uint4 v = *reinterpret_cast<const uint4*>(cp + 8 * gu);
+                  e[4 * u] = v.x; e[4 * u + 1] = v.y; e[4 * u + 2] = v.z; e[4 * u + 3] = v.w;
+                  // the unit's NBITS residual bytes; e = h(cent + w) with the packed fp16 adds of ms_decode, weights from the small table
+                  uint32_t rw[2] = {0u, 0u};
+                  if constexpr (NBITS == 1) rw[0] = rp[gu];
+                  else if constexpr (NBITS == 2) rw[0] = *reinterpret_cast<const uint16_t*>(rp + 2 * gu);
+                  else if constexpr (NBITS == 4) rw[0] = *reinterpret_cast<const uint32_t*>(rp + 4 * gu);
+                  else { const uint2 w = *reinterpret_cast<const uint2*>(rp + 8 * gu); rw[0] = w.x; rw[1] = w.y; }
+#pragma unroll
+                  for (int kk = 0; kk < NBITS; ++kk) {
+                    const uint32_t byte = (rw[kk >> 2] >> (8 * (kk & 3))) & 0xFFu;
+                    if constexpr (PB >= 2) {
+#pragma unroll
+                      for (int j = 0; j < PB / 2; ++j) {
+                        const uint32_t wv = *reinterpret_cast<const uint32_t*>(&slut[byte * PB + 2 * j]);
+                        const int ei = 4 * u + kk * (PB / 2) + j;
+                        e[ei] = h2_as_u32(u32_as_h2(e[ei]) + u32_as_h2(wv));
+                      }
+                    } else if ((kk & 1) == 0) {   // nbits 8: two bytes make one packed register
+                      const uint32_t byte1 = (rw[(kk + 1) >> 2] >> (8 * ((kk + 1) & 3))) & 0xFFu;
+                      const uint32_t wv = (uint32_t)slut[byte] | ((uint32_t)slut[byte1] << 16);
+                      e[4 * u + kk / 2] = h2_as_u32(u32_as_h2(e[4 * u + kk / 2]) + u32_as_h2(wv));
+                    }
+                  }
+                  norm_pair2(e[4 * u], e[4 * u + 1], r_hi, r_lo);
+                  norm_pair2(e[4 * u + 2], e[4 * u + 3], r_hi, r_lo);
+                }
+              }
+#pragma unroll
+              for (int j = 0; j < MSR_G; ++j) {
+                if (cols[j] < 0) continue;
+                const uint32_t* qq = reinterpret_cast<const uint32_t*>(qpad + ((int64_t)b * Qp + ch * 32 + cols[j]) * D + 128 * sl);   // uniform address
+                // the reference's chain, spelled as in k_maxsim_repair (see the comment there)
+                float ac = acc[j];
+#pragma unroll
+                for (int u = 0; u < 16; ++u) {
+                  if (u < nus) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                      const uint32_t qv = qq[4 * u + i];
+                      asm volatile("v_fma_mix_f32 %0, %1, %2, %0 op_sel_hi:[1,1,0]\n\ts_nop 0\n\t"
+                                   "v_fma_mix_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[1,1,0]\n\ts_nop 0"
+                                   : "+v"(ac) : "v"(e[4 * u + i]), "v"(qv));
+                    }
+                  }
+                }
+                acc[j] = ac;
+              }
+            }
+#pragma unroll
+            for (int j = 0; j < MSR_G; ++j) {
+              if (cols[j] < 0) continue;
+              float sim = live ? (float)(half_t)acc[j] : NEG_MASK_F;
+#pragma unroll
+              for (int sft = 32; sft > 0; sft >>= 1) { const float o = __shfl_xor(sim, sft, 64); sim = o > sim ? o : sim; }
+              if (lane == cols[j]) colmax = sim > colmax ? sim : colmax;   // (a NaN sim is dropped, as in k_maxsim_repair)
+            }
+          }
+        }
+        if (lane < 32 && ((fm >> lane) & 1u)) {
+          cv = colmax;
+          cm16[slot * Qp + q] = __builtin_bit_cast(uint16_t, (half_t)colmax);
+        }
+        if (lane == 0) flags[slot * nflag + ch] = 0u;
+      }
+      // the score re-summed as k_maxsim_sl sums it: column after column in ascending order (the reference's order)
+#pragma unroll
+      for (int l = 0; l < 32; ++l) total += __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(cv), l));
+    }
+    if (lane == 0) {
+      exact[slot] = total;
+      unc[slot] = 0.f;
+    }
+  }
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------
 static int ms_num_cus() {
   static int cus[64] = {0};
@@ -1336,9 +1870,13 @@ static int ms_num_cus() {
   return cus[dev];
 }
 
-bool fpk_maxsim_fast_shape(int dim, int nbits) {
+// FP_TEST=ms_sliced=0 (A/B runs): the shapes without a k_maxsim6 / k_maxsim5 instantiation go back to k_maxsim_generic
+static bool ms_sliced_on() { static const bool on = fp_test_opt("ms_sliced", 1) != 0; return on; }
+static bool ms_fixed_shape(int dim, int nbits) {   // k_maxsim5 / k_maxsim6 and k_maxsim_repair<D, NBITS>
   return ((dim == 96 || dim == 48) && (nbits == 4 || nbits == 2)) || ms6_shape(dim, nbits);
 }
+bool fpk_maxsim_fast_shape(int dim, int nbits) { return ms_fixed_shape(dim, nbits) || ms_sliced_on(); }
+bool fpk_maxsim_fixed_shape(int dim, int nbits) { return ms_fixed_shape(dim, nbits); }
 bool fpk_maxsim6_shape(int dim, int nbits) { return ms6_shape(dim, nbits); }
 
 __global__ __launch_bounds__(256) void k_resid_native(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int64_t n, int pr, int nbits, int nu) {
@@ -1420,6 +1958,42 @@ static void launch_maxsim5(const FpIndexDev& ix, const uint16_t* qpad, const FpS
   }
 }
 
+// LDS of k_maxsim_sl: table + B fragments (1 KiB per 16-column group and k-step) + windows.  Two column chunks per launch
+// where that fits the 160 KiB of a workgroup (dim <= 736), else one chunk per launch with `accumulate`.
+static size_t mssl_lds(int dim, int nch) { return MS_LUT_BYTES + (size_t)nch * 2 * ((dim + 31) / 32) * 64 * 16 + (size_t)nch * 32 * 4; }
+static bool mssl_pair(int dim) { return mssl_lds(dim, 2) <= 160 * 1024; }
+
+template <int NBITS>
+static void launch_maxsim_sl(const FpIndexDev& ix, const uint16_t* qpad, const FpSearchShape& sh, const int32_t* sel_pid, const int64_t* pref,
+                             int64_t Rcap, float* exact, const FpMaxsimAux& aux, hipStream_t st) {
+  const int nch = sh.Qp / 32;
+  const int64_t tot_max = (int64_t)sh.B * Rcap;
+  auto grid_for = [&](int waves) {
+    int g = ms_num_cus();
+    if ((int64_t)g * waves > tot_max) g = (int)std::max<int64_t>(1, (tot_max + waves - 1) / waves);
+    return g;
+  };
+  const float eps_env = 1.9073486e-06f;   // 2^-19
+  const float eps_rel = eps_env * (ix.dim > 128 ? (float)ix.dim / 128.f : 1.f);   // as launch_maxsim6
+  MsArgs a{ix.centroids, ix.lut, ix.codes, ix.norms, ix.residuals, ix.doc_off, qpad, sel_pid, pref, exact, aux.cm16, aux.unc, aux.uncm, aux.flags,
+           Rcap, sh.B, sh.Q, sh.Qp, 0, 0, eps_rel, nullptr, 0};
+  static std::atomic<uint64_t> ok1{0}, ok2{0};
+  fp_allow_big_lds((const void*)k_maxsim_sl<NBITS, 1>, ok1, 160 * 1024);
+  fp_allow_big_lds((const void*)k_maxsim_sl<NBITS, 2>, ok2, 160 * 1024);
+  const bool pair = mssl_pair(ix.dim);
+  for (int ch = 0; ch < nch;) {
+    a.ch_begin = ch;
+    if (pair && nch - ch >= 2) {
+      hipLaunchKernelGGL((k_maxsim_sl<NBITS, 2>), dim3((unsigned)grid_for(MSSL_WAVES)), dim3(MSSL_WAVES * 64), mssl_lds(ix.dim, 2), st, a, ix.dim);
+      ch += 2;
+    } else {
+      hipLaunchKernelGGL((k_maxsim_sl<NBITS, 1>), dim3((unsigned)grid_for(MSSL_WAVES)), dim3(MSSL_WAVES * 64), mssl_lds(ix.dim, 1), st, a, ix.dim);
+      ch += 1;
+    }
+    a.accumulate = 1;
+  }
+}
+
 // exact scores of the rerank lists.  pref: [B+1] int64 scratch.  aux (all nullable together): per-column maxima, uncertainty
 // budgets and flag masks for the exact-order repair.  Returns 0, or -1 when q_len is too large for the generic kernel.
 int fpk_maxsim(const FpIndexDev& ix, const uint16_t* qpad, const FpSearchShape& sh, const int32_t* sel_pid, const int32_t* sel_cnt,
@@ -1445,6 +2019,16 @@ int fpk_maxsim(const FpIndexDev& ix, const uint16_t* qpad, const FpSearchShape& 
   }
   MS_CASE(96, 2) MS_CASE(48, 4) MS_CASE(48, 2)   // k_maxsim5: the fast shapes k_maxsim6 has no instantiation for (dim not a multiple of 32, 6-byte lane chunks)
 #undef MS_CASE
+  if (ms_sliced_on()) {   // every other shape: the K-sliced MFMA kernel
+    if (!pref_ready) hipLaunchKernelGGL(k_cnt_prefix, dim3(1), dim3(256), 0, st, sel_cnt, sh.B, pref);
+    switch (ix.nbits) {
+      case 1: launch_maxsim_sl<1>(ix, qpad, sh, sel_pid, pref, Rcap, exact, aux, st); break;
+      case 2: launch_maxsim_sl<2>(ix, qpad, sh, sel_pid, pref, Rcap, exact, aux, st); break;
+      case 4: launch_maxsim_sl<4>(ix, qpad, sh, sel_pid, pref, Rcap, exact, aux, st); break;
+      default: launch_maxsim_sl<8>(ix, qpad, sh, sel_pid, pref, Rcap, exact, aux, st); break;
+    }
+    return 0;
+  }
   const int qcap = (sh.Q + 63) / 64 > 8 ? 8 : (sh.Q + 63) / 64;
   hipLaunchKernelGGL(k_maxsim_generic, dim3((unsigned)Rcap, (unsigned)sh.B), dim3(64), (size_t)ix.dim * 4, st, ix.centroids, ix.lut, ix.codes,
                      ix.norms, ix.residuals, ix.doc_off, ix.dim, ix.nbits, qpad, sh.Q, sh.Qp, sel_pid, sel_cnt, Rcap, exact, aux.unc, qcap);
@@ -1455,13 +2039,19 @@ int fpk_maxsim(const FpIndexDev& ix, const uint16_t* qpad, const FpSearchShape& 
 // marks the flagged documents that are near-tied in the final ranking (marks / nmark), or nothing when npow2 keys do not fit LDS
 int fpk_final_mark(const float* score, const float* unc, const float* uncm, const int32_t* cnt, int64_t stride, int B, int64_t top_k, int32_t* marks,
                    int32_t* nmark,
-                   hipStream_t st, uint32_t* flat_n, void* flat) {
+                   hipStream_t st, uint32_t* flat_n, void* flat, bool emit_exact) {
   int np2 = fp_next_pow2((int)stride);
   if (np2 < 2) np2 = 2;
   if (np2 > 8192) return -1;   // 16 B of LDS per entry, 16 scan elements per thread
-  static std::atomic<uint64_t> lds_ok{0};
-  fp_allow_big_lds((const void*)k_final_mark, lds_ok, 136 * 1024);
-  hipLaunchKernelGGL(k_final_mark, dim3((unsigned)B), dim3(1024), (size_t)np2 * 16, st, score, unc, uncm, cnt, stride, np2, top_k, marks, nmark,
+  static std::atomic<uint64_t> lds_ok{0}, lds_ok_e{0};
+  if (emit_exact) {
+    fp_allow_big_lds((const void*)k_final_mark<true>, lds_ok_e, 136 * 1024);
+    hipLaunchKernelGGL(k_final_mark<true>, dim3((unsigned)B), dim3(1024), (size_t)np2 * 16, st, score, unc, uncm, cnt, stride, np2, top_k, marks,
+                       nmark, flat_n, static_cast<uint2*>(flat));
+    return 0;
+  }
+  fp_allow_big_lds((const void*)k_final_mark<false>, lds_ok, 136 * 1024);
+  hipLaunchKernelGGL(k_final_mark<false>, dim3((unsigned)B), dim3(1024), (size_t)np2 * 16, st, score, unc, uncm, cnt, stride, np2, top_k, marks, nmark,
                      flat_n, static_cast<uint2*>(flat));
   return 0;
 }
@@ -1485,4 +2075,12 @@ void fpk_maxsim_repair(const FpIndexDev& ix, const uint16_t* qpad, const FpSearc
   MS_CASE(128, 4) MS_CASE(128, 2) MS_CASE(128, 8) MS_CASE(128, 1) MS_CASE(96, 4) MS_CASE(96, 2) MS_CASE(64, 4) MS_CASE(64, 2) MS_CASE(48, 4) MS_CASE(48, 2)
   MS_CASE(256, 4) MS_CASE(256, 2)
 #undef MS_CASE
+#define MSSL_CASE(NB_) \
+  case NB_: \
+    hipLaunchKernelGGL((k_maxsim_repair_sl<NB_>), grid, dim3(64), 0, st, ix.centroids, ix.lut, ix.codes, ix.norms, ix.residuals, ix.doc_off, ix.dim, \
+                       qpad, sh.Q, sh.Qp, sel_pid, sel_cnt, Rcap, marks, nmark, exact, aux.unc, aux.cm16, aux.flags, flat_n, \
+                       static_cast<const uint2*>(flat)); \
+    break;
+  switch (ix.nbits) { MSSL_CASE(1) MSSL_CASE(2) MSSL_CASE(4) MSSL_CASE(8) }
+#undef MSSL_CASE
 }

@@ -232,8 +232,8 @@ int fp_last_s1_counts(uint64_t* out, int cap);
  * exact-order repair.  scores [n]; col_max [n, q_len] f16 bits = per query column the maximum over the document's tokens as the
  * kernel rounds it; unc [n] = uncertainty budget (sum of the fp16 ulps of the flagged columns); flags [n, ceil(q_len/32)] = bit
  * per flagged column (a column is flagged when its fp32 maximum lies so close to an fp16 rounding boundary that the
- * reference's summation order could round it the other way).  Shapes without an MFMA kernel: col_max / flags come back zero
- * (that path is exact: nothing is ever flagged).  Any output but scores may be NULL. */
+ * reference's summation order could round it the other way).  col_max / flags / unc are filled for every (dim, nbits) the index
+ * accepts: each has an MFMA kernel.  Any output but scores may be NULL. */
 int fp_maxsim_columns(const fp_index* index, const uint16_t* query_f16, int32_t q_len, int32_t dim, const int64_t* pids, int64_t n,
                       float* scores, uint16_t* col_max, float* unc, uint32_t* flags);
 
