@@ -65,6 +65,7 @@ SYMBOLS = {
     "fp_graph_replay_count": (C.c_uint64, []),
     "fp_reconstruct_embeddings": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp]),
     "fp_compress": (C.c_int, [C.c_int, _vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp]),
+    "fp_compress_last_counts": (C.c_int, [_vp, C.c_int]),
     "fp_assign_l2": (C.c_int, [C.c_int, _vp, _vp, _i64, _i32, _vp, _i64, _vp]),
     "fp_kmeans": (C.c_int, [C.c_int, _vp, _i64, _i32, _i64, _i32, _vp, C.c_uint64, _vp, _vp]),
     "fp_kmeans_last_timings": (C.c_int, [_vp, C.c_int]),

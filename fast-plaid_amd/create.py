@@ -42,6 +42,17 @@ def compress(centroids, bucket_cutoffs, embeddings, nbits: int, device: str = "c
     return codes, res
 
 
+def last_compress_counts() -> dict | None:
+    """Of the calling thread's last `compress`: chunks, those that took an MFMA narrowing, those of them sent on to the exact kernel,
+    the device microseconds of the assignment and of the residual packing, and -- under FP_TEST=assign_stats=1, else 0 -- the sum and
+    the maximum over the tokens of the candidates the narrowing counted; None when that call failed."""
+    out = (N.C.c_int64 * 7)()
+    if N.lib().fp_compress_last_counts(out, 7) <= 0:
+        return None
+    return dict(chunks=out[0], narrowed_chunks=out[1], fallback_chunks=out[2], assign_us=out[3], pack_us=out[4], cand_sum=out[5],
+                cand_max=out[6])
+
+
 def cutoffs_for_f32_compare(cutoffs_f32) -> np.ndarray:
     """create.rs:413 compares the fp16 residuals with the FLOAT cutoffs it has just computed (torch.bucketize promotes), while the
     device kernel (and update.rs, through the loader's Half cast) compares with fp16 cutoffs.  For an fp16 residual r and an fp32

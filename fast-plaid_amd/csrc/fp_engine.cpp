@@ -1998,22 +1998,43 @@ extern "C" int fp_token_scores(const fp_index* cix, const uint16_t* queries, int
 // ------------------------------------------------------------------------------------------
 // index creation, device part (create.rs:148-184, :404-428)
 // ------------------------------------------------------------------------------------------
+// dims of the nearest-centroid assignment (fp_index_ops.hip): [1, 256], and every multiple of 8 up to 1024
+static bool assign_dim_accepted(int32_t dim) { return dim >= 1 && (dim <= 256 || (dim <= 1024 && dim % 8 == 0)); }
+
+enum { CP_CHUNKS, CP_NARROWED, CP_FALLBACK, CP_US_ASSIGN, CP_US_PACK, CP_CAND_SUM, CP_CAND_MAX, CP_N };
+static thread_local int64_t g_cp[CP_N];
+static thread_local int g_cp_have = 0;   // 1: the figures are those of a call that succeeded
+extern "C" int fp_compress_last_counts(int64_t* out, int cap) {
+  if (!out || cap < 0) return 0;
+  for (int i = 0; i < std::min(cap, (int)CP_N); ++i) out[i] = g_cp[i];
+  return g_cp_have;
+}
+
 extern "C" int fp_compress(int device_id, const uint16_t* centroids, int64_t C, int32_t dim, int32_t nbits, const uint16_t* cutoffs,
                            const uint16_t* emb, int64_t T, int64_t* out_codes, uint8_t* out_res) {
+  g_cp_have = 0;
+  for (int64_t& v : g_cp) v = 0;
   if (!centroids || !cutoffs || C < 1 || T < 0 || (T > 0 && (!emb || !out_codes || !out_res))) return fail(FP_EINVAL, "bad argument");
   if (!(nbits == 1 || nbits == 2 || nbits == 4 || nbits == 8)) return fail(FP_EINVAL, "nbits must divide 8 (1, 2, 4 or 8)");
-  if (dim < 1 || dim > 256 || (dim * nbits) % 8 != 0) return fail(FP_EUNSUPPORTED, "fp_compress: dim must be in [1, 256] with dim * nbits a multiple of 8");
+  if (!assign_dim_accepted(dim) || (dim * nbits) % 8 != 0)
+    return fail(FP_EUNSUPPORTED, "fp_compress: dim must be in [1, 256] or a multiple of 8 up to 1024, with dim * nbits a multiple of 8");
   if (C >= 0x7FFFFFFFll) return fail(FP_EUNSUPPORTED, "too many centroids");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(FP_EHIP, "no HIP device available (this library has no CPU path)");
   if (device_id < 0 || device_id >= ndev) return fail(FP_EINVAL, "device index out of range");
   HIPCHK(fp_set_device(device_id));
-  if (T == 0) return FP_OK;
+  int64_t cp[CP_N] = {0, 0, 0, 0, 0, 0, 0};
+  if (T == 0) {
+    for (int i = 0; i < CP_N; ++i) g_cp[i] = cp[i];
+    g_cp_have = 1;
+    return FP_OK;
+  }
   const int pr = dim * nbits / 8;
   const int64_t CHUNK = 1ll << 20;   // tokens per pass
   const int64_t cap = std::min<int64_t>(T, CHUNK);
   void *d_cent = nullptr, *d_cut = nullptr, *d_emb = nullptr, *d_c32 = nullptr, *d_c64 = nullptr, *d_out = nullptr, *d_work = nullptr;
   hipStream_t st = nullptr;
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
   int rc = FP_OK;
   float cmaxabs = 0.f;   // bounds the MFMA summation error in the assignment (fp16 -> float by hand: no device needed)
   for (int64_t i = 0; i < C * dim; ++i) {
@@ -2025,6 +2046,8 @@ extern "C" int fp_compress(int device_id, const uint16_t* centroids, int64_t C, 
   auto cleanup = [&]() {
     for (void* p : {d_cent, d_cut, d_emb, d_c32, d_c64, d_out, d_work})
       if (p) (void)hipFree(p);
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
     if (st) (void)hipStreamDestroy(st);
   };
 #define CCHK(x)                                                                                   \
@@ -2036,6 +2059,7 @@ extern "C" int fp_compress(int device_id, const uint16_t* centroids, int64_t C, 
     }                                                                                             \
   } while (0)
   CCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  for (hipEvent_t& e : ev) CCHK(hipEventCreate(&e));
   CCHK(hipMalloc(&d_cent, (size_t)C * dim * 2));
   CCHK(hipMalloc(&d_cut, 1024));   // up to 255 cutoffs (nbits = 8)
   CCHK(hipMalloc(&d_emb, (size_t)cap * dim * 2));
@@ -2048,25 +2072,38 @@ extern "C" int fp_compress(int device_id, const uint16_t* centroids, int64_t C, 
   for (int64_t t0 = 0; t0 < T && rc == FP_OK; t0 += CHUNK) {
     const int64_t n = std::min<int64_t>(CHUNK, T - t0);
     CCHK(hipMemcpyAsync(d_emb, emb + t0 * dim, (size_t)n * dim * 2, hipMemcpyHostToDevice, st));
+    int64_t how[4] = {0, 0, 0, 0};
     if (fpk_compress(static_cast<const uint16_t*>(d_emb), n, static_cast<const uint16_t*>(d_cent), C, dim, nbits,
                      static_cast<const uint16_t*>(d_cut), cmaxabs, static_cast<int32_t*>(d_c32), static_cast<int64_t*>(d_c64),
-                     static_cast<uint8_t*>(d_out), d_work, st)) {
+                     static_cast<uint8_t*>(d_out), d_work, st, how, ev)) {
       cleanup();
       return fail(FP_EUNSUPPORTED, "dim");
     }
     CCHK(hipMemcpyAsync(out_codes + t0, d_c64, (size_t)n * 8, hipMemcpyDeviceToHost, st));
     CCHK(hipMemcpyAsync(out_res + t0 * pr, d_out, (size_t)n * pr, hipMemcpyDeviceToHost, st));
     CCHK(hipStreamSynchronize(st));
+    ++cp[CP_CHUNKS];
+    cp[CP_NARROWED] += how[0];
+    cp[CP_FALLBACK] += how[1];
+    cp[CP_CAND_SUM] += how[2];
+    cp[CP_CAND_MAX] = std::max(cp[CP_CAND_MAX], how[3]);
+    for (int s = 0; s < 2; ++s) {
+      float ms = 0.f;
+      CCHK(hipEventElapsedTime(&ms, ev[s], ev[s + 1]));
+      cp[CP_US_ASSIGN + s] += (int64_t)(ms * 1000.f + 0.5f);
+    }
   }
 #undef CCHK
   cleanup();
+  for (int i = 0; i < CP_N; ++i) g_cp[i] = cp[i];
+  g_cp_have = 1;
   return rc;
 }
 
 extern "C" int fp_assign_l2(int device_id, const uint16_t* centroids, const float* half_sqnorm, int64_t C, int32_t dim, const uint16_t* emb,
                             int64_t T, int64_t* out_labels) {
   if (!centroids || !half_sqnorm || C < 1 || T < 0 || (T > 0 && (!emb || !out_labels))) return fail(FP_EINVAL, "bad argument");
-  if (dim < 1 || dim > 256) return fail(FP_EUNSUPPORTED, "fp_assign_l2: dim must be in [1, 256]");
+  if (!assign_dim_accepted(dim)) return fail(FP_EUNSUPPORTED, "fp_assign_l2: dim must be in [1, 256] or a multiple of 8 up to 1024");
   if (C >= 0x7FFFFFFFll) return fail(FP_EUNSUPPORTED, "too many centroids");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(FP_EHIP, "no HIP device available (this library has no CPU path)");

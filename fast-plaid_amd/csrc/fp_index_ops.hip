@@ -3,6 +3,7 @@
 // arithmetic self-test.
 #include <algorithm>
 #include <atomic>
+#include <vector>
 
 #include "fp_internal.h"
 
@@ -149,12 +150,18 @@ int fpk_token_scores(const FpIndexDev& ix, const uint16_t* queries, int Q, const
 // one ascending-k fp32 chain per (token, centroid): 64 tokens x 64 centroids per tile, 4x4 outputs per thread, operands
 // in LDS as fp32.  Ties go to the lowest centroid index (torch.argmax: first maximal value).
 // L2 = true (k-means assignment): score = dot - half_sqnorm[c] compared in fp32 instead of the fp16-rounded dot.
+#define ASSIGN_EXACT_SLICE 256   // 2 x 64 x (slice + 1) fp32 operand tiles + 8 KiB must fit the 160 KiB of LDS
 template <bool L2>
 __global__ __launch_bounds__(256) void k_assign_exact(const uint16_t* __restrict__ emb, int64_t T, const uint16_t* __restrict__ cent,
                                                       int64_t C, const float* __restrict__ half_sqnorm, int32_t* __restrict__ codes, int D) {
-  // any dim (runtime): As / Bs [64][D + 1] fp32 and best_s [64][16] in dynamic LDS
+  // any dim (runtime): As / Bs [64][DS + 1] fp32 and best_s [64][16] in dynamic LDS, DS = min(D, ASSIGN_EXACT_SLICE).  D above
+  // one slice: the contraction is walked in slices of DS dims in ascending order, acc[4][4] carried across them and both tiles
+  // staged again per slice -- every accumulator is still the one ascending-k chain.  D within one slice: the token tile is staged
+  // once, as before.
   extern __shared__ __attribute__((aligned(16))) unsigned char xsm[];
-  const int ld = D + 1;
+  const int DS = D < ASSIGN_EXACT_SLICE ? D : ASSIGN_EXACT_SLICE;
+  const bool one = D <= DS;
+  const int ld = DS + 1;
   float* As_ = reinterpret_cast<float*>(xsm);
   float* Bs_ = As_ + 64 * ld;
   unsigned long long (*best_s)[16] = reinterpret_cast<unsigned long long (*)[16]>(xsm + (size_t)2 * 64 * ld * 4);
@@ -163,33 +170,38 @@ __global__ __launch_bounds__(256) void k_assign_exact(const uint16_t* __restrict
   const int tid = threadIdx.x;
   const int tr = tid >> 4, tc = tid & 15;       // 16 x 16 threads, 4 rows x 4 cols each
   const int64_t t0 = (int64_t)blockIdx.x * 64;
-  for (int i = tid; i < 64 * D; i += 256) {
-    const int r = i / D, d = i % D;
-    As(r, d) = (t0 + r < T) ? (float)__builtin_bit_cast(half_t, emb[(t0 + r) * D + d]) : 0.f;
-  }
-  unsigned long long best[4] = {0ull, 0ull, 0ull, 0ull};
-  for (int64_t c0 = 0; c0 < C; c0 += 64) {
-    __syncthreads();
+  if (one)
     for (int i = tid; i < 64 * D; i += 256) {
       const int r = i / D, d = i % D;
-      Bs(r, d) = (c0 + r < C) ? (float)__builtin_bit_cast(half_t, cent[(c0 + r) * D + d]) : 0.f;
+      As(r, d) = (t0 + r < T) ? (float)__builtin_bit_cast(half_t, emb[(t0 + r) * D + d]) : 0.f;
     }
-    __syncthreads();
+  unsigned long long best[4] = {0ull, 0ull, 0ull, 0ull};
+  for (int64_t c0 = 0; c0 < C; c0 += 64) {
     float acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
-    for (int kk = 0; kk < D; ++kk) {   // ascending k: each accumulator is the reference's chain (products of fp16 pairs are exact in fp32)
-      float a[4], b[4];
+    for (int k0 = 0; k0 < D; k0 += DS) {
+      const int w = D - k0 < DS ? D - k0 : DS;
+      __syncthreads();
+      for (int i = tid; i < 64 * w; i += 256) {
+        const int r = i / w, d = i % w;
+        if (!one) As(r, d) = (t0 + r < T) ? (float)__builtin_bit_cast(half_t, emb[(t0 + r) * D + k0 + d]) : 0.f;
+        Bs(r, d) = (c0 + r < C) ? (float)__builtin_bit_cast(half_t, cent[(c0 + r) * D + k0 + d]) : 0.f;
+      }
+      __syncthreads();
+      for (int kk = 0; kk < w; ++kk) {   // ascending k: each accumulator is the reference's chain (products of fp16 pairs are exact in fp32)
+        float a[4], b[4];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) a[i] = As(tr * 4 + i, kk);
+        for (int i = 0; i < 4; ++i) a[i] = As(tr * 4 + i, kk);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) b[j] = Bs(tc + 16 * j, kk);
+        for (int j = 0; j < 4; ++j) b[j] = Bs(tc + 16 * j, kk);
 #pragma unroll
-      for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] += a[i] * b[j];
+          for (int j = 0; j < 4; ++j) acc[i][j] += a[i] * b[j];
+      }
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -220,8 +232,10 @@ __global__ __launch_bounds__(256) void k_assign_exact(const uint16_t* __restrict
 #undef As
 #undef Bs
 }
-static size_t assign_exact_lds(int D) { return (size_t)2 * 64 * (D + 1) * 4 + 64 * 16 * 8; }
-#define ASSIGN_MAX_DIM 256   // 2 x 64 x (D+1) fp32 operand tiles + 8 KiB must fit the 160 KiB of LDS
+static size_t assign_exact_lds(int D) { return (size_t)2 * 64 * (std::min(D, ASSIGN_EXACT_SLICE) + 1) * 4 + 64 * 16 * 8; }
+// dims the assignment accepts: [1, 256] as ever (one slice of the exact kernel), and every multiple of 8 up to ASSIGN_MAX_DIM
+#define ASSIGN_MAX_DIM 1024
+static bool assign_dim_ok(int D) { return D >= 1 && (D <= ASSIGN_EXACT_SLICE || (D <= ASSIGN_MAX_DIM && D % 8 == 0)); }
 
 // ---- MFMA fast path of the nearest-centroid search, still exact -------------------------------------------------------
 // The exact kernel above runs at 30 TFLOP/s.  MFMA sums in another order, so its scores cannot decide near-ties; but they
@@ -338,6 +352,187 @@ __global__ __launch_bounds__(256) void k_assign_mfma(const uint16_t* __restrict_
   }
 }
 
+// ---- the same two passes at a runtime dim: the contraction walked in K-slices ---------------------------------------------
+// D: any multiple of 8 from 8 to ASSIGN_MAX_DIM.  Contract, ASSIGN_CAP, per-lane state and per-tile epilogue are k_assign_mfma's;
+// what differs is how the operands reach the MFMA.  Neither tile fits LDS whole (128 rows of dim 1024 are 256 KB), so BOTH are
+// streamed in slices of SL_DIMS = 64 dims: a stage holds the token slice and the centroid slice ([128][128 B] each, 16-byte units
+// XOR-swizzled by row & 7 as in k_assign_mfma<64>), two stages make 64 KB and let two workgroups share a CU.  The fp32
+// accumulators of the (token tile, centroid tile) pair -- 128 x 128 outputs, 64 registers per lane -- stay in registers across
+// the slices of a pair and are reset after its epilogue.
+// Pipeline: the (centroid tile, slice) pairs form ONE sequence of steps.  In step s every thread first issues the 8 global
+// 16-byte loads of step s + 1 (4 token units, 4 centroid units) into registers, then feeds the MFMA from stage s & 1, then
+// stores the registers to stage (s + 1) & 1 and meets the one barrier of the step.  Stage (s + 1) & 1 was last read in step
+// s - 1, which every wave left through that step's barrier, so the stores race with no read; the loads are in flight for the
+// whole MFMA section, across tile boundaries too.  The token slices are read again for every centroid tile: a token tile is at
+// most 256 KB and stays in L2.
+// Ragged last slice (D % 64 != 0) and rows past T / C: the absent 16-byte units are stored as zeros.  A zero operand gives a zero
+// product, and a zero term changes no fp32 sum in any order, so the scores are those of a D-term contraction.  MFMA steps whose
+// two units are both absent are skipped (uniform branch).
+// Soundness of the narrowing: k_assign_thr / k_assign_thr_l2 bound |MFMA sum - ascending chain| for ANY summation order of the
+// D exact fp16 x fp16 products (both are within (D - 1) 2^-24 sum|products| of the true sum), and k_assign_recheck evaluates the
+// chain itself.  Neither argument uses the order in which this kernel or k_assign_mfma adds, so both hold unchanged here.
+#define SL_DIMS 64
+#define SL_ROWB (SL_DIMS * 2)          // bytes of a row's slice
+#define SL_TILEB (128 * SL_ROWB)       // one operand slice of a stage
+#define SL_STAGEB (2 * SL_TILEB)
+static constexpr size_t ASSIGN_SL_LDS = 2 * SL_STAGEB;   // 64 KB
+template <int PASS, bool L2>
+__global__ __launch_bounds__(256, 2) void k_assign_mfma_sl(const uint16_t* __restrict__ emb, int64_t T, const uint16_t* __restrict__ cent, int64_t C,
+                                                        float* __restrict__ tmax /*PASS 1 out*/, const float* __restrict__ thr /*PASS 2 in*/,
+                                                        int32_t* __restrict__ ccnt, int32_t* __restrict__ ccand,
+                                                        const float* __restrict__ half_sqnorm /*L2 only*/, int D) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int tid = threadIdx.x;
+  const int64_t t0 = (int64_t)blockIdx.x * 128;
+  const int wave = tid >> 6, lane = tid & 63;
+  const int wr = wave >> 1, wc = wave & 1;
+  const int l31 = lane & 31, hi = lane >> 5;
+  const int U = D >> 3;                       // 16-byte units of a row
+  const int NS = (D + SL_DIMS - 1) / SL_DIMS;   // slices of the contraction
+  const int64_t nct = (C + 127) / 128;
+  const int64_t nstep = nct * NS;
+  // this thread's part of a stage: unit lj of rows lr + 32 q (q = 0..3) of both tiles
+  const int lr = tid >> 3, lj = tid & 7;
+  const int lpos = lr * SL_ROWB + ((lj ^ (lr & 7)) * 16);   // (lr + 32 q) & 7 == lr & 7
+  const uint16_t* tsrc[4];
+  bool tin[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int64_t t = t0 + lr + 32 * q;
+    tin[q] = t < T;
+    tsrc[q] = emb + (tin[q] ? t : 0) * D;
+  }
+  uint4 pt[4], pc[4];
+  auto fetch = [&](int64_t ct, int ks) {   // the global loads of step (ct, ks)
+    const int u = ks * (SL_DIMS / 8) + lj;
+    const bool uin = u < U;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      pt[q] = make_uint4(0, 0, 0, 0);
+      pc[q] = make_uint4(0, 0, 0, 0);
+      if (uin && tin[q]) pt[q] = *reinterpret_cast<const uint4*>(tsrc[q] + u * 8);
+      const int64_t c = ct * 128 + lr + 32 * q;
+      if (uin && c < C) pc[q] = *reinterpret_cast<const uint4*>(cent + c * D + u * 8);
+    }
+  };
+  auto stash = [&](int stage) {
+    unsigned char* base = smem + stage * SL_STAGEB + lpos;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      *reinterpret_cast<uint4*>(base + q * 32 * SL_ROWB) = pt[q];
+      *reinterpret_cast<uint4*>(base + SL_TILEB + q * 32 * SL_ROWB) = pc[q];
+    }
+  };
+  fetch(0, 0);
+  // per-lane state over this lane's centroid columns: running maxima (pass 1) or the thresholds of its 32 token rows (pass 2)
+  float st[2][16];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      if (PASS == 1) {
+        st[a][r] = -INFINITY;
+      } else {
+        const int64_t t = t0 + wr * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+        st[a][r] = (t < T) ? thr[t] : INFINITY;
+      }
+    }
+  stash(0);
+  __syncthreads();
+  f16v acc[2][2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+  // LDS offsets of this lane's operand rows inside a tile slice; the unit index is XORed in per MFMA step
+  int aoff[2], boff[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    aoff[t] = (wr * 64 + t * 32 + l31) * SL_ROWB;
+    boff[t] = SL_TILEB + (wc * 64 + t * 32 + l31) * SL_ROWB;
+  }
+  const int sw = l31 & 7;   // (row & 7) of all four rows
+  int64_t ct = 0;
+  int ks = 0;
+  for (int64_t s = 0; s < nstep; ++s) {
+    int ksn = ks + 1;
+    int64_t ctn = ct;
+    if (ksn == NS) {
+      ksn = 0;
+      ++ctn;
+    }
+    const bool more = s + 1 < nstep;
+    if (more) fetch(ctn, ksn);
+    const unsigned char* sb = smem + (int)(s & 1) * SL_STAGEB;
+    const int units = U - ks * (SL_DIMS / 8);   // units present in this slice (>= 1; 8 or more: a full slice)
+#pragma unroll
+    for (int k = 0; k < SL_DIMS / 16; ++k) {
+      if (2 * k < units) {
+        h8 af[2], bf[2];
+        const int j = ((k * 2 + hi) ^ sw) * 16;
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          af[t] = *reinterpret_cast<const h8*>(sb + aoff[t] + j);
+          bf[t] = *reinterpret_cast<const h8*>(sb + boff[t] + j);
+        }
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int b = 0; b < 2; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[a], bf[b], acc[a][b], 0, 0, 0);
+      }
+    }
+    if (ksn == 0) {   // last slice of the pair: k_assign_mfma's epilogue, then fresh accumulators
+      const int64_t c0 = ct * 128;
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        const int64_t c = c0 + wc * 64 + b * 32 + l31;
+        if (c < C) {
+          float hn = 0.f;
+          if constexpr (L2) hn = half_sqnorm[c];
+#pragma unroll
+          for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              float v = acc[a][b][r];
+              if constexpr (L2) v -= hn;
+              if (PASS == 1) {
+                st[a][r] = fmaxf(st[a][r], v);
+              } else if (v >= st[a][r]) {
+                const int64_t t = t0 + wr * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                const int pos = atomicAdd(&ccnt[t], 1);
+                if (pos < ASSIGN_CAP) ccand[t * ASSIGN_CAP + pos] = (int32_t)c;
+              }
+            }
+        }
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+      }
+    }
+    if (more) stash((int)((s + 1) & 1));
+    __syncthreads();
+    ks = ksn;
+    ct = ctn;
+  }
+  if (PASS == 1) {
+    float (*red)[128] = reinterpret_cast<float (*)[128]>(smem);   // every stage has been read: the last step ended in a barrier
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        float v = st[a][r];
+#pragma unroll
+        for (int sft = 1; sft < 32; sft <<= 1) v = fmaxf(v, __shfl_xor(v, sft, 64));
+        if (l31 == 0) red[wc][wr * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi] = v;
+      }
+    __syncthreads();
+    if (tid < 128 && t0 + tid < T) tmax[t0 + tid] = fmaxf(red[0][tid], red[1][tid]);
+  }
+}
+
 // thr[t] = m - (two fp16 ulps at |m| + twice the worst-case fp32 summation error of a D-term dot product of this token).
 // Why the true winner w is collected: h is monotone, so exact_w > exact_c - ulp16 for every c (else h(exact_c) > h(exact_w));
 // with c* = argmax of the MFMA scores and |mfma - exact| <= eps:  mfma_w >= exact_w - eps > exact_c* - ulp16 - eps >= m - ulp16 - 2 eps.
@@ -441,11 +636,12 @@ __global__ __launch_bounds__(256) void k_quantize_pack(const uint16_t* __restric
 // scratch: tmax / thr f32 [T], ccnt i32 [T], ccand i32 [T * ASSIGN_CAP], overflow i32 [1]  (all inside `work`, see fpk_compress_work_bytes)
 size_t fpk_compress_work_bytes(int64_t T) { return (size_t)T * (4 + 4 + 4 + 4 * ASSIGN_CAP) + 64; }
 
-// pass 1 -> threshold -> pass 2 -> re-check of one chunk on `st` (D 64 or 128); *overflow is zeroed first and counts the tokens
-// whose candidate list overflowed.  L2: the k-means score (half_sqnorm, stat = k_assign_thr_l2's device-side maxima)
+// pass 1 -> threshold -> pass 2 -> re-check of one chunk on `st`; *overflow is zeroed first and counts the tokens whose candidate
+// list overflowed.  L2: the k-means score (half_sqnorm, stat = k_assign_thr_l2's device-side maxima).  D = 64 / 128: k_assign_mfma<D>;
+// D = 0: the K-sliced kernel at the runtime dim `Drt`
 static int32_t* assign_work_overflow(void* work, int64_t T) { return reinterpret_cast<int32_t*>(static_cast<char*>(work) + (size_t)T * (12 + 4 * ASSIGN_CAP)); }
 template <int D, bool L2>
-static void assign_narrow_d(const uint16_t* emb, int64_t T, const uint16_t* cent, int64_t C, float cmaxabs, const uint32_t* stat,
+static void assign_narrow_d(const uint16_t* emb, int64_t T, const uint16_t* cent, int64_t C, int Drt, float cmaxabs, const uint32_t* stat,
                             const float* half_sqnorm, int32_t* codes32, void* work, int32_t* overflow, hipStream_t st) {
   float* tmax = static_cast<float*>(work);
   float* thr = tmax + T;
@@ -453,34 +649,58 @@ static void assign_narrow_d(const uint16_t* emb, int64_t T, const uint16_t* cent
   int32_t* ccand = ccnt + T;
   const unsigned mblocks = (unsigned)((T + 127) / 128);
   const unsigned tblocks = fp_grid_cap((T + 255) / 256, 256);
-  const size_t lds = (size_t)2 * 128 * D * 2;
   (void)hipMemsetAsync(overflow, 0, 4, st);
-  if (D == 128) {
+  auto threshold = [&]() {
+    if (L2)
+      hipLaunchKernelGGL(k_assign_thr_l2, dim3(tblocks), dim3(256), 0, st, emb, T, Drt, stat, tmax, thr, ccnt);
+    else
+      hipLaunchKernelGGL(k_assign_thr, dim3(tblocks), dim3(256), 0, st, emb, T, Drt, cmaxabs, tmax, thr, ccnt);
+  };
+  if constexpr (D == 0) {
     static std::atomic<uint64_t> ok1{0}, ok2{0};
-    fp_allow_big_lds((const void*)k_assign_mfma<D, 1, L2>, ok1, 80 * 1024);
-    fp_allow_big_lds((const void*)k_assign_mfma<D, 2, L2>, ok2, 80 * 1024);
+    fp_allow_big_lds((const void*)k_assign_mfma_sl<1, L2>, ok1, (int)ASSIGN_SL_LDS);
+    fp_allow_big_lds((const void*)k_assign_mfma_sl<2, L2>, ok2, (int)ASSIGN_SL_LDS);
+    hipLaunchKernelGGL((k_assign_mfma_sl<1, L2>), dim3(mblocks), dim3(256), ASSIGN_SL_LDS, st, emb, T, cent, C, tmax, (const float*)nullptr,
+                       (int32_t*)nullptr, (int32_t*)nullptr, half_sqnorm, Drt);
+    threshold();
+    hipLaunchKernelGGL((k_assign_mfma_sl<2, L2>), dim3(mblocks), dim3(256), ASSIGN_SL_LDS, st, emb, T, cent, C, (float*)nullptr, thr, ccnt, ccand,
+                       half_sqnorm, Drt);
+  } else {
+    const size_t lds = (size_t)2 * 128 * D * 2;
+    if (D == 128) {
+      static std::atomic<uint64_t> ok1{0}, ok2{0};
+      fp_allow_big_lds((const void*)k_assign_mfma<D, 1, L2>, ok1, 80 * 1024);
+      fp_allow_big_lds((const void*)k_assign_mfma<D, 2, L2>, ok2, 80 * 1024);
+    }
+    hipLaunchKernelGGL((k_assign_mfma<D, 1, L2>), dim3(mblocks), dim3(256), lds, st, emb, T, cent, C, tmax, (const float*)nullptr, (int32_t*)nullptr,
+                       (int32_t*)nullptr, half_sqnorm);
+    threshold();
+    hipLaunchKernelGGL((k_assign_mfma<D, 2, L2>), dim3(mblocks), dim3(256), lds, st, emb, T, cent, C, (float*)nullptr, thr, ccnt, ccand, half_sqnorm);
   }
-  hipLaunchKernelGGL((k_assign_mfma<D, 1, L2>), dim3(mblocks), dim3(256), lds, st, emb, T, cent, C, tmax, (const float*)nullptr, (int32_t*)nullptr,
-                     (int32_t*)nullptr, half_sqnorm);
-  if (L2)
-    hipLaunchKernelGGL(k_assign_thr_l2, dim3(tblocks), dim3(256), 0, st, emb, T, D, stat, tmax, thr, ccnt);
-  else
-    hipLaunchKernelGGL(k_assign_thr, dim3(tblocks), dim3(256), 0, st, emb, T, D, cmaxabs, tmax, thr, ccnt);
-  hipLaunchKernelGGL((k_assign_mfma<D, 2, L2>), dim3(mblocks), dim3(256), lds, st, emb, T, cent, C, (float*)nullptr, thr, ccnt, ccand, half_sqnorm);
-  hipLaunchKernelGGL((k_assign_recheck<L2>), dim3(tblocks), dim3(256), 0, st, emb, T, cent, D, ccnt, ccand, codes32, overflow, half_sqnorm);
+  hipLaunchKernelGGL((k_assign_recheck<L2>), dim3(tblocks), dim3(256), 0, st, emb, T, cent, Drt, ccnt, ccand, codes32, overflow, half_sqnorm);
+}
+// the dims that take the narrowing: every multiple of 8 up to ASSIGN_MAX_DIM, on tables of at least 256 centroids (a smaller
+// table is as fast through the exact kernel); FP_TEST=assign_exact=1 turns it off (tools/bench_compress.py, tests)
+static bool assign_narrows(int64_t C, int D) {
+  static const int exact_env = fp_test_opt("assign_exact", 0) != 0 ? 1 : 0;
+  return !exact_env && C >= 256 && D % 8 == 0;
 }
 template <bool L2>
 static void assign_narrow(const uint16_t* emb, int64_t T, const uint16_t* cent, int64_t C, int D, float cmaxabs, const uint32_t* stat,
                           const float* half_sqnorm, int32_t* codes32, void* work, int32_t* overflow, hipStream_t st) {
-  if (D == 128)
-    assign_narrow_d<128, L2>(emb, T, cent, C, cmaxabs, stat, half_sqnorm, codes32, work, overflow, st);
+  static const int sliced_env = fp_test_opt("assign_sliced", 0) != 0 ? 1 : 0;   // dim 64 / 128 through the K-sliced kernel too (tests)
+  if (D == 128 && !sliced_env)
+    assign_narrow_d<128, L2>(emb, T, cent, C, D, cmaxabs, stat, half_sqnorm, codes32, work, overflow, st);
+  else if (D == 64 && !sliced_env)
+    assign_narrow_d<64, L2>(emb, T, cent, C, D, cmaxabs, stat, half_sqnorm, codes32, work, overflow, st);
   else
-    assign_narrow_d<64, L2>(emb, T, cent, C, cmaxabs, stat, half_sqnorm, codes32, work, overflow, st);
+    assign_narrow_d<0, L2>(emb, T, cent, C, D, cmaxabs, stat, half_sqnorm, codes32, work, overflow, st);
 }
 
+// how[0] = 1: the chunk took the narrowing, how[1] = 1: and went on to the exact kernel; how[2..3]: sum and maximum of ccnt over the
+// chunk's tokens, copied back only under FP_TEST=assign_stats=1 (tools/bench_compress.py: how close a dim sits to ASSIGN_CAP)
 static int assign_codes(const uint16_t* emb, int64_t T, const uint16_t* cent, int64_t C, int D, float cmaxabs, int32_t* codes32, void* work,
-                        hipStream_t st) {
-  static const int impl_env = fp_test_opt("assign_exact", 0) != 0 ? 1 : 0;   // the all-VALU exact kernel only (tools/bench_compress.py)
+                        hipStream_t st, int64_t* how) {
   const unsigned eblocks = fp_grid_cap((T + 63) / 64, 256);
   if ((int64_t)eblocks * 64 < T) return -2;   // callers chunk far below this
   auto exact = [&]() {
@@ -488,26 +708,45 @@ static int assign_codes(const uint16_t* emb, int64_t T, const uint16_t* cent, in
     fp_allow_big_lds((const void*)k_assign_exact<false>, ok, 160 * 1024);
     hipLaunchKernelGGL((k_assign_exact<false>), dim3(eblocks), dim3(256), assign_exact_lds(D), st, emb, T, cent, C, (const float*)nullptr, codes32, D);
   };
-  if (D < 1 || D > ASSIGN_MAX_DIM) return -1;
-  if (impl_env || !work || C < 256 || (D != 128 && D != 64)) {   // tiny tables: the exact kernel is as fast; the MFMA narrowing is built for dim 64 / 128
+  if (!assign_dim_ok(D)) return -1;
+  how[0] = how[1] = how[2] = how[3] = 0;
+  if (!work || !assign_narrows(C, D)) {
     exact();
     return 0;
   }
+  how[0] = 1;
   int32_t* overflow = assign_work_overflow(work, T);
   assign_narrow<false>(emb, T, cent, C, D, cmaxabs, nullptr, nullptr, codes32, work, overflow, st);
   int32_t h_over = 0;
   if (hipMemcpyAsync(&h_over, overflow, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -3;
-  if (h_over > 0) exact();   // a token met more than ASSIGN_CAP near-tied centroids: the whole chunk goes through the exact kernel
+  static const int stats_env = fp_test_opt("assign_stats", 0) != 0 ? 1 : 0;
+  if (stats_env) {
+    std::vector<int32_t> h_cnt((size_t)T);
+    if (hipMemcpy(h_cnt.data(), static_cast<char*>(work) + (size_t)T * 8, (size_t)T * 4, hipMemcpyDeviceToHost) != hipSuccess) return -3;
+    for (int32_t n : h_cnt) {
+      how[2] += n;
+      how[3] = std::max<int64_t>(how[3], n);
+    }
+  }
+  if (h_over > 0) {   // a token met more than ASSIGN_CAP near-tied centroids: the whole chunk goes through the exact kernel
+    how[1] = 1;
+    exact();
+  }
   return 0;
 }
 
 int fpk_compress(const uint16_t* emb, int64_t T, const uint16_t* cent, int64_t C, int D, int nbits, const uint16_t* cutoffs, float cmaxabs,
-                 int32_t* codes32, int64_t* codes64, uint8_t* out, void* work, hipStream_t st) {
+                 int32_t* codes32, int64_t* codes64, uint8_t* out, void* work, hipStream_t st, int64_t* how, hipEvent_t* ev) {
+  int64_t how_[4] = {0, 0, 0, 0};
+  if (!how) how = how_;
   if (T <= 0) return 0;
-  if (int rc = assign_codes(emb, T, cent, C, D, cmaxabs, codes32, work, st)) return rc;
+  if (ev) (void)hipEventRecord(ev[0], st);
+  if (int rc = assign_codes(emb, T, cent, C, D, cmaxabs, codes32, work, st, how)) return rc;
+  if (ev) (void)hipEventRecord(ev[1], st);
   const int64_t total = T * (D * nbits / 8);
   hipLaunchKernelGGL(k_quantize_pack, dim3(fp_grid_cap((total + 255) / 256, 256)), dim3(256), 0, st, emb, cent, codes32, cutoffs, D, nbits, T, out,
                      codes64);
+  if (ev) (void)hipEventRecord(ev[2], st);
   return 0;
 }
 
@@ -520,21 +759,20 @@ int fpk_assign_l2_exact(const uint16_t* emb, int64_t T, const uint16_t* cent, co
   if (T <= 0) return 0;
   const unsigned blocks = fp_grid_cap((T + 63) / 64, 256);
   if ((int64_t)blocks * 64 < T) return -2;
-  if (D < 1 || D > ASSIGN_MAX_DIM) return -1;
+  if (!assign_dim_ok(D)) return -1;
   static std::atomic<uint64_t> ok{0};
   fp_allow_big_lds((const void*)k_assign_exact<true>, ok, 160 * 1024);
   hipLaunchKernelGGL((k_assign_exact<true>), dim3(blocks), dim3(256), assign_exact_lds(D), st, emb, T, cent, C, half_sqnorm, codes32, D);
   return 0;
 }
 
-// k-means assignment of one chunk with the MFMA narrowing (fp_kmeans): labels for dim 64 / 128 and C >= 256, nothing read back.
+// k-means assignment of one chunk with the MFMA narrowing (fp_kmeans): labels for a dim that is a multiple of 8 and C >= 256, nothing read back.
 // Returns 1 when the chunk took the narrowing -- the caller reads *overflow after the stream has drained and sends a chunk with a
 // non-zero count through fpk_assign_l2_exact -- 0 when it went straight to the exact kernel, < 0 as fpk_assign_l2.
 int fpk_assign_l2_narrow(const uint16_t* emb, int64_t T, const uint16_t* cent, const float* half_sqnorm, const uint32_t* stat, int64_t C, int D,
                          int32_t* codes32, void* work, int32_t* overflow, hipStream_t st) {
-  static const int exact_env = fp_test_opt("assign_exact", 0) != 0 ? 1 : 0;
   if (T <= 0) return 0;
-  if (exact_env || !work || C < 256 || (D != 128 && D != 64)) return fpk_assign_l2_exact(emb, T, cent, half_sqnorm, C, D, codes32, st);
+  if (!work || !assign_dim_ok(D) || !assign_narrows(C, D)) return fpk_assign_l2_exact(emb, T, cent, half_sqnorm, C, D, codes32, st);
   if ((T + 127) / 128 > 0x7FFFFFll) return -2;
   assign_narrow<true>(emb, T, cent, C, D, 0.f, stat, half_sqnorm, codes32, work, overflow, st);
   return 1;

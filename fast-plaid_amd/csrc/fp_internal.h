@@ -418,18 +418,22 @@ void fpk_narrow_i64_i32(const int64_t* in, int32_t* out, int64_t n, int64_t add,
 void fpk_ivf_check_sorted(const int64_t* off, const int32_t* pids, int64_t P, uint32_t* flag, hipStream_t st);
 // create.rs:148-184, :404-428 on device pointers: nearest centroid (MFMA narrowing + exact re-check of the near-ties, or the exact
 // kernel alone; codes32 scratch, codes64 output) + quantised packed residuals.  cmaxabs = max |centroid element| (bounds the MFMA
-// summation error); work = fpk_compress_work_bytes(T) bytes of device scratch (nullptr: exact kernel only).
+// summation error); work = fpk_compress_work_bytes(T) bytes of device scratch (nullptr: exact kernel only).  dim: [1, 256] or a
+// multiple of 8 up to 1024; a multiple of 8 with C >= 256 takes the narrowing (k_assign_mfma<D> at 64 / 128, else the K-sliced
+// kernel).  how (nullable, [4]): [0] = 1 when the chunk took the narrowing, [1] = 1 when it then went to the exact kernel, [2..3] = sum and
+// maximum over the tokens of the candidates pass 2 counted (under FP_TEST=assign_stats=1, else 0); ev
+// (nullable): three events recorded before the assignment, after it and after the packing.
 // -1 unsupported dim, -2 chunk too large, -3 HIP error
 size_t fpk_compress_work_bytes(int64_t T);
 int fpk_compress(const uint16_t* emb, int64_t T, const uint16_t* cent, int64_t C, int D, int nbits, const uint16_t* cutoffs, float cmaxabs,
-                 int32_t* codes32, int64_t* codes64, uint8_t* out, void* work, hipStream_t st);
+                 int32_t* codes32, int64_t* codes64, uint8_t* out, void* work, hipStream_t st, int64_t* how = nullptr, hipEvent_t* ev = nullptr);
 // k-means assignment step: argmax_c (dot - half_sqnorm[c]) in fp32, ties -> lowest index
 int fpk_assign_l2(const uint16_t* emb, int64_t T, const uint16_t* cent, const float* half_sqnorm, int64_t C, int D, int32_t* codes32,
                   int64_t* codes64, hipStream_t st);
 // the same without the widening (fp_kmeans keeps 32-bit labels on the device) ...
 int fpk_assign_l2_exact(const uint16_t* emb, int64_t T, const uint16_t* cent, const float* half_sqnorm, int64_t C, int D, int32_t* codes32,
                         hipStream_t st);
-// ... and through the MFMA narrowing (dim 64 / 128, C >= 256; else the exact kernel): see fp_index_ops.hip.  stat = device
+// ... and through the MFMA narrowing (dim a multiple of 8, C >= 256; else the exact kernel): see fp_index_ops.hip.  stat = device
 // {max|cent|, max half_sqnorm} as fp32 bits; work = fpk_compress_work_bytes(T); 1: narrowed, *overflow to be read by the caller
 int fpk_assign_l2_narrow(const uint16_t* emb, int64_t T, const uint16_t* cent, const float* half_sqnorm, const uint32_t* stat, int64_t C, int D,
                          int32_t* codes32, void* work, int32_t* overflow, hipStream_t st);

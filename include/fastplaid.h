@@ -256,14 +256,27 @@ int fp_token_scores(const fp_index* index, const uint16_t* queries_f16, int32_t 
  *   bucket    = #{ i : cutoffs[i] < r }                          (torch.bucketize, right=False)
  *   bytes     = each bucket as nbits bits LSB first, the bit stream packed 8 per byte big-endian.
  * Stand-alone (no index handle): host buffers in and out, processed in device-sized chunks.
+ * dim: 1 .. 256, or any multiple of 8 up to 1024 (every dim an index accepts), with dim * nbits a multiple of 8; else
+ * FP_EUNSUPPORTED.  A dim that is a multiple of 8, on a table of at least 256 centroids, narrows the argmax with two MFMA passes
+ * (a fixed-dim kernel at 64 / 128, one K-sliced kernel at a runtime dim elsewhere) and re-checks the near-ties with the ascending-k
+ * chain; a chunk in which a token meets more than 8 near-tied centroids, every other dim and every smaller table go through the
+ * all-chain kernel, which walks a dim above 256 in slices of 256.  The codes are the same on every path.
  * Codec training (quantiles) and file writing stay on the host (fast-plaid_amd/create.py); k-means has fp_kmeans below. */
 int fp_compress(int device_id, const uint16_t* centroids_f16 /*[n_centroids, dim]*/, int64_t n_centroids, int32_t dim, int32_t nbits,
                 const uint16_t* bucket_cutoffs_f16 /*[2^nbits - 1]*/, const uint16_t* embeddings_f16 /*[n_tokens, dim]*/,
                 int64_t n_tokens, int64_t* out_codes /*[n_tokens]*/, uint8_t* out_residuals /*[n_tokens, dim*nbits/8]*/);
 
+/* Of the calling thread's last fp_compress call: out[0..2] = chunks processed, chunks that took an MFMA narrowing, and those of them
+ * sent on to the all-chain kernel; out[3..4] = device microseconds (HIP events, summed over the chunks) of the assignment and of
+ * the residual packing; out[5..6] = sum and maximum over the tokens of the candidates pass 2 of the narrowing counted (the count, not
+ * capped at 8), copied back only under FP_TEST=assign_stats=1 (it then sits inside out[3]), else 0.  Returns 1 when that call
+ * succeeded, else 0 (out == NULL, or the call failed: the figures are then all zero). */
+int fp_compress_last_counts(int64_t* out, int cap);
+
 /* K-means assignment step for the Python k-means driver (python/fast_plaid/search/fast_plaid.py:71-185 calls the
  * external fastkmeans package; its Lloyd iteration assigns every point to the centroid of least squared L2 distance):
- * out_labels[t] = argmax_c ( emb[t] . cent[c] - half_sqnorm[c] ), fp32, ties -> lowest index. */
+ * out_labels[t] = argmax_c ( emb[t] . cent[c] - half_sqnorm[c] ), fp32, ties -> lowest index.  dim as fp_compress: 1 .. 256, or a
+ * multiple of 8 up to 1024.  Always the all-chain kernel: the yardstick the narrowed labels of fp_kmeans are compared with. */
 int fp_assign_l2(int device_id, const uint16_t* centroids_f16 /*[n_centroids, dim]*/, const float* half_sqnorm /*[n_centroids]*/,
                  int64_t n_centroids, int32_t dim, const uint16_t* embeddings_f16 /*[n_tokens, dim]*/, int64_t n_tokens,
                  int64_t* out_labels /*[n_tokens]*/);
@@ -275,8 +288,8 @@ int fp_assign_l2(int device_id, const uint16_t* centroids_f16 /*[n_centroids, di
  *   for it = 0 .. niter-1:
  *   2. cent16 = fp16(cent32), round to nearest even;  hn[c] = 0.5f * (ascending-d fp32 chain of cent16[c][d]^2)
  *   3. label[t] = argmax_c fl32(chain(t, c) - hn[c]), chain = the ascending-d fp32 sum of data[t][d] * cent16[c][d], ties -> the
- *      lowest c: what fp_assign_l2 returns for the same cent16 and hn (dim 64 / 128 with k >= 256 narrow the search with two MFMA
- *      passes and re-check the near-ties with that chain; the labels are the same)
+ *      lowest c: what fp_assign_l2 returns for the same cent16 and hn (a dim that is a multiple of 8 with k >= 256 narrows the search
+ *      with two MFMA passes, as fp_compress does, and re-checks the near-ties with that chain; the labels are the same)
  *   4. S[c][d] = the EXACT sum of data[t][d] over label[t] == c, cnt[c] the count.  Every finite fp16 value is an integer multiple
  *      of 2^-24; the sums are int64 integers in that unit, so they do not depend on the order of the additions
  *   5. cnt[c] > 0:  cent32[c][d] = (float)(((double)S_int * 2^-24) / (double)cnt[c]), every step round to nearest even
@@ -302,8 +315,8 @@ int fp_kmeans_last_timings(float* ms, int cap);
  * fp32 sum of exact fp16 x fp16 products, so fused and unfused accumulation give the same bits:
  *   hn[c]      = 0.5f * chain of cent[c][d]^2, on the device                            (fp_kmeans step 2, not a pairwise sum)
  *   nearest[t] = argmax_c fl32(chain(x_t . cent_c) - hn[c]), ties -> the lowest c        (what fp_assign_l2 returns for that hn;
- *                dim 64 / 128 with >= 256 centroids narrow the search with two MFMA passes and re-check the near-ties with the
- *                chain, and a chunk whose candidate list overflows goes through the exact kernel: the labels are the same)
+ *                a dim that is a multiple of 8 with >= 256 centroids narrows the search with two MFMA passes, as fp_compress
+ *                does, and re-checks the near-ties with the chain, and a chunk whose candidate list overflows goes through the exact kernel: the labels are the same)
  *   s[t]       = that maximal value;  x2[t] = chain of x_t[d]^2
  *   sqdist[t]  = fl32(x2[t] - 2 s[t])                                                   (2 s is exact: the reference's
  *                x^2 + y^2 - 2xy with the rounding points pinned; a few ulps below zero for a token that equals a centroid)
