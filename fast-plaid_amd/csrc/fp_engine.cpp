@@ -1942,7 +1942,9 @@ extern "C" int fp_reconstruct_embeddings(const fp_index* cix, const int64_t* doc
   HIPCHK(s->tok_idx.ensure((size_t)rows * 8));
   HIPCHK(s->recon.ensure((size_t)rows * ix->d.dim * 4));
   HIPCHK(hipMemcpyAsync(s->tok_idx.p, tok.data(), (size_t)rows * 8, hipMemcpyHostToDevice, s->st));
-  fpk_reconstruct(ix->d, s->tok_idx.as<int64_t>(), rows, s->recon.as<float>(), s->st);
+  if (fpk_tok_tiled()) fpk_reconstruct_units(ix->d, s->tok_idx.as<int64_t>(), rows, s->recon.as<float>(), s->st);
+  else if (ix->d.dim > 512) return fail(FP_EUNSUPPORTED, "FP_TEST=tok_tiled=0: k_reconstruct serves dim <= 512 only");
+  else fpk_reconstruct(ix->d, s->tok_idx.as<int64_t>(), rows, s->recon.as<float>(), s->st);
   HIPCHK(hipMemcpyAsync(out, s->recon.p, (size_t)rows * ix->d.dim * 4, hipMemcpyDeviceToHost, s->st));
   HIPCHK(hipStreamSynchronize(s->st));
   return FP_OK;
@@ -1958,7 +1960,8 @@ extern "C" int fp_token_scores(const fp_index* cix, const uint16_t* queries, int
   if (dim != ix->d.dim) return fail(FP_EINVAL, "query dim does not match the index");
   if (Q < 1) return fail(FP_EINVAL, "need at least one query token");
   HIPCHK(fp_set_device(ix->device));
-  std::vector<int32_t> hq, hp;
+  std::vector<int32_t> hq, hp, tiles;   // tiles: {hit, first stored token, first query row} per 64 x 64 tile (k_token_scores_tile)
+  const bool tiled = fpk_tok_tiled();
   int64_t off = 0, h = 0;
   out_offsets[0] = 0;
   for (int32_t b = 0; b < nq; ++b) {
@@ -1966,7 +1969,12 @@ extern "C" int fp_token_scores(const fp_index* cix, const uint16_t* queries, int
     for (int32_t i = 0; i < counts[b]; ++i) {
       const int64_t d = pids[(int64_t)b * stride + i] - ix->d.pid_offset;
       if (d < 0 || d >= ix->d.N) return fail(FP_EINVAL, "document id out of range");
-      off += (int64_t)Q * (ix->h_doc_off[d + 1] - ix->h_doc_off[d]);
+      if (h >= 0x7FFFFFFFll) return fail(FP_EUNSUPPORTED, "more than 2^31 - 1 hits in one call");
+      const int64_t len = ix->h_doc_off[d + 1] - ix->h_doc_off[d];
+      if (out && tiled)
+        for (int64_t s0 = 0; s0 < len; s0 += 64)
+          for (int32_t j0 = 0; j0 < Q; j0 += 64) tiles.insert(tiles.end(), {(int32_t)h, (int32_t)s0, j0});
+      off += (int64_t)Q * len;
       out_offsets[++h] = off;
       hq.push_back(b);
       hp.push_back((int32_t)d);
@@ -1979,7 +1987,7 @@ extern "C" int fp_token_scores(const fp_index* cix, const uint16_t* queries, int
   struct Rel { fp_index* ix; Scratch* s; ~Rel() { release(ix, s); } } rel{ix, s};
   const size_t qbytes = (size_t)nq * Q * dim * 2;
   HIPCHK(s->qin.ensure(qbytes));
-  HIPCHK(s->tok_idx.ensure((size_t)h * 8 + (size_t)h * 8 + 64));   // hit_query | hit_pid (i32 each) + out offsets (i64)
+  HIPCHK(s->tok_idx.ensure((size_t)h * 8 + tiles.size() * 4 + 64));   // hit_query | hit_pid (i32 each) | tiles (3 x i32 each)
   HIPCHK(s->tmpp.ensure((size_t)(h + 1) * 8));
   HIPCHK(s->recon.ensure((size_t)off * 2));
   int32_t* d_hq = s->tok_idx.as<int32_t>();
@@ -1988,8 +1996,14 @@ extern "C" int fp_token_scores(const fp_index* cix, const uint16_t* queries, int
   HIPCHK(hipMemcpyAsync(d_hq, hq.data(), (size_t)h * 4, hipMemcpyHostToDevice, s->st));
   HIPCHK(hipMemcpyAsync(d_hp, hp.data(), (size_t)h * 4, hipMemcpyHostToDevice, s->st));
   HIPCHK(hipMemcpyAsync(s->tmpp.p, out_offsets, (size_t)(h + 1) * 8, hipMemcpyHostToDevice, s->st));
-  if (fpk_token_scores(ix->d, s->qin.as<uint16_t>(), Q, d_hq, d_hp, h, s->tmpp.as<int64_t>(), s->recon.as<uint16_t>(), s->st))
+  if (tiled) {
+    int32_t* d_tiles = d_hp + h;
+    HIPCHK(hipMemcpyAsync(d_tiles, tiles.data(), tiles.size() * 4, hipMemcpyHostToDevice, s->st));
+    fpk_token_scores_tile(ix->d, s->qin.as<uint16_t>(), Q, d_hq, d_hp, s->tmpp.as<int64_t>(), d_tiles, (int64_t)(tiles.size() / 3),
+                          s->recon.as<uint16_t>(), s->st);
+  } else if (fpk_token_scores(ix->d, s->qin.as<uint16_t>(), Q, d_hq, d_hp, h, s->tmpp.as<int64_t>(), s->recon.as<uint16_t>(), s->st)) {
     return fail(FP_EUNSUPPORTED, "q_len * dim too large for the token-score kernel");
+  }
   HIPCHK(hipMemcpyAsync(out, s->recon.p, (size_t)off * 2, hipMemcpyDeviceToHost, s->st));
   HIPCHK(hipStreamSynchronize(s->st));
   return FP_OK;

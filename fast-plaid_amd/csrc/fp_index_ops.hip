@@ -43,6 +43,8 @@ void fpk_ivf_check_sorted(const int64_t* off, const int32_t* pids, int64_t P, ui
   hipLaunchKernelGGL(k_ivf_check_sorted, dim3(fp_grid_cap((P + 3) / 4, 256)), dim3(256), 0, st, off, pids, P, flag);
 }
 
+// k_reconstruct / k_token_scores: the round-1 kernels, reachable under FP_TEST=tok_tiled=0 only (A/B runs); the default path is
+// fp_token_scores.hip.  k_reconstruct serves dim <= 512 (its LDS row), k_token_scores (q_len + 1) * dim * 4 B up to 150 KB.
 // reconstruct_embeddings (embeddings.rs:12-69): decompress rows to fp32.  One 64-thread
 // block per token; the fp32 sum of squares is taken in ascending-dim order by one lane so
 // the result is bit-identical to the CPU reference order.

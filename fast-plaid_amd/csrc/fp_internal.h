@@ -1,4 +1,4 @@
-// Internal declarations shared by the HIP kernels (fp_kernels.hip, fp_index_ops.hip, fp_kmeans.hip, fp_outliers.hip, fp_maxsim.hip, fp_synth.hip) and the
+// Internal declarations shared by the HIP kernels (fp_kernels.hip, fp_index_ops.hip, fp_token_scores.hip, fp_kmeans.hip, fp_outliers.hip, fp_maxsim.hip, fp_synth.hip) and the
 // host engine (fp_engine.cpp).  Not part of the C ABI (see include/fastplaid.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -470,6 +470,13 @@ int fpk_token_scores(const FpIndexDev& ix, const uint16_t* queries, int Q, const
                      const int64_t* out_off, uint16_t* out, hipStream_t st);
 void fpk_reconstruct(const FpIndexDev& ix, const int64_t* tok_idx /*[n] global token rows*/, int64_t n, float* out,
                      hipStream_t st);
+// ---- fp_token_scores.hip: both operations at every dim and q_len an index accepts (the default path) ----
+bool fpk_tok_tiled();   // false under FP_TEST=tok_tiled=0: the two kernels above, with their limits (A/B runs)
+// tiles [n_tiles][3] = {hit, first stored token of the document's 64-token block, first row of the 64-row query block}
+void fpk_token_scores_tile(const FpIndexDev& ix, const uint16_t* queries, int Q, const int32_t* hit_query, const int32_t* hit_pid,
+                           const int64_t* out_off, const int32_t* tiles, int64_t n_tiles, uint16_t* out, hipStream_t st);
+void fpk_reconstruct_units(const FpIndexDev& ix, const int64_t* tok_idx /*[n] global token rows*/, int64_t n, float* out,
+                           hipStream_t st);
 
 void fpk_selftest_arith(unsigned long long* out_dev /*[2], zeroed*/, hipStream_t st);
 // the fence-free "last workgroup finishes the job" pattern checked on this device: 0 = holds (synchronises `st`)

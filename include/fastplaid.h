@@ -244,7 +244,10 @@ int fp_maxsim_columns(const fp_index* index, const uint16_t* query_f16, int32_t 
  * token order, row-major, at out + out_offsets[h] (hits ordered query-major, then rank).
  * Call fp_search first and pass its pids / counts.  With out == NULL only out_offsets
  * [n_hits + 1] (element offsets) is filled, so the caller can size `out`; out_capacity is in
- * elements.  Ids outside the index give FP_EINVAL. */
+ * elements.  Ids outside the index give FP_EINVAL.
+ * Accepted range: every (dim, nbits) an index accepts (dim a multiple of 8 up to 1024) and any q_len >= 1 -- the work is cut
+ * into tiles of 64 document tokens x 64 query tokens whose LDS footprint does not depend on dim or q_len; up to 2^31 - 1 hits per
+ * call (FP_EUNSUPPORTED beyond).  Every entry is one ascending-k fp32 chain rounded once to fp16: the reference's bits. */
 int fp_token_scores(const fp_index* index, const uint16_t* queries_f16, int32_t n_queries, int32_t q_len, int32_t dim,
                     const int64_t* pids /*[n_queries, stride]*/, const int32_t* counts /*[n_queries]*/, int64_t stride,
                     int64_t* out_offsets /*[sum(counts) + 1]*/, uint16_t* out /*f16, nullable*/, int64_t out_capacity);
@@ -338,7 +341,8 @@ int fp_centroid_outliers_last_counts(int64_t* out, int cap);
 /* ---- `reconstruct_embeddings` (rust/utils/embeddings.rs:12-69) ----------------------- */
 /* Decompresses whole documents to fp32 rows. out: host [sum(len(doc)) , dim] f32 in the
  * order of doc_ids (ids may repeat); out_lengths [n]. `out_capacity_rows` guards the buffer: when it is too small the call fails
- * with FP_EINVAL AFTER filling out_lengths for every requested document, so sum(out_lengths) is the capacity to come back with. */
+ * with FP_EINVAL AFTER filling out_lengths for every requested document, so sum(out_lengths) is the capacity to come back with.
+ * Accepted range: every (dim, nbits) an index accepts (dim a multiple of 8 up to 1024); rows are the reference's bits. */
 int fp_reconstruct_embeddings(const fp_index* index, const int64_t* doc_ids, int64_t n, float* out,
                               int64_t out_capacity_rows, int64_t* out_lengths);
 
