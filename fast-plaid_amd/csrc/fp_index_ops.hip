@@ -538,6 +538,14 @@ __global__ __launch_bounds__(256, 2) void k_assign_mfma_sl(const uint16_t* __res
 // thr[t] = m - (two fp16 ulps at |m| + twice the worst-case fp32 summation error of a D-term dot product of this token).
 // Why the true winner w is collected: h is monotone, so exact_w > exact_c - ulp16 for every c (else h(exact_c) > h(exact_w));
 // with c* = argmax of the MFMA scores and |mfma - exact| <= eps:  mfma_w >= exact_w - eps > exact_c* - ulp16 - eps >= m - ulp16 - 2 eps.
+// That argument needs a finite ulp16, and h has none beyond fp16's range: h(x) = +inf for every x >= 65520, -inf for x <= -65520.
+//   +inf: every centroid whose chain reaches 65520 ties at +inf and the lowest index among them wins, however far below m its
+//         score lies.  Each of them has mfma >= 65520 - eps, so thr never exceeds 65520 - 2 eps: all of them are collected (when
+//         no chain reaches 65520 the lower threshold only collects more, and the finite argument above still holds).
+//   -inf: when m <= -65520 + 2 eps the chain of c* can lie at or below -65520, and then every score is -inf and index 0 wins:
+//         thr = -inf collects every centroid, the list overflows (a narrowed table has at least 256) and the chunk goes to
+//         k_assign_exact.  With m above that, h(exact_c*) is finite and so is the winner's: the finite argument holds.
+// (unnormalised fp16 embeddings reach this range at dim 128 with entries around 23)
 __global__ void k_assign_thr(const uint16_t* __restrict__ emb, int64_t T, int D, float cmaxabs, const float* __restrict__ tmax,
                              float* __restrict__ thr, int32_t* __restrict__ ccnt) {
   for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < T; t += (int64_t)gridDim.x * blockDim.x) {
@@ -546,7 +554,8 @@ __global__ void k_assign_thr(const uint16_t* __restrict__ emb, int64_t T, int D,
     const float m = tmax[t];
     const float ulp2 = __builtin_fmaxf(__builtin_fabsf(m), 6.103515625e-05f) * 0.001953125f;   // 2^-9 |m|  >= 2 ulp16
     const float eps2 = l1 * cmaxabs * (float)D * 1.1920929e-07f * 2.0f;                          // 2 * D * 2^-23 * sum|x_k| max|c|
-    thr[t] = m - (ulp2 + eps2);
+    const float fin = __builtin_fminf(m - (ulp2 + eps2), 65520.0f - eps2);
+    thr[t] = m <= eps2 - 65520.0f ? -INFINITY : fin;
     ccnt[t] = 0;
   }
 }

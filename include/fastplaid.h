@@ -263,7 +263,9 @@ int fp_token_scores(const fp_index* index, const uint16_t* queries_f16, int32_t 
  * FP_EUNSUPPORTED.  A dim that is a multiple of 8, on a table of at least 256 centroids, narrows the argmax with two MFMA passes
  * (a fixed-dim kernel at 64 / 128, one K-sliced kernel at a runtime dim elsewhere) and re-checks the near-ties with the ascending-k
  * chain; a chunk in which a token meets more than 8 near-tied centroids, every other dim and every smaller table go through the
- * all-chain kernel, which walks a dim above 256 in slices of 256.  The codes are the same on every path.
+ * all-chain kernel, which walks a dim above 256 in slices of 256.  The codes are the same on every path, beyond fp16's range too:
+ * h(x) = +inf for every chain >= 65520, so all such centroids tie and the lowest index among them wins (the narrowing collects
+ * every centroid that can reach +inf), and a token whose scores are all -inf gets code 0 (its chunk goes to the all-chain kernel).
  * Codec training (quantiles) and file writing stay on the host (fast-plaid_amd/create.py); k-means has fp_kmeans below. */
 int fp_compress(int device_id, const uint16_t* centroids_f16 /*[n_centroids, dim]*/, int64_t n_centroids, int32_t dim, int32_t nbits,
                 const uint16_t* bucket_cutoffs_f16 /*[2^nbits - 1]*/, const uint16_t* embeddings_f16 /*[n_tokens, dim]*/,
