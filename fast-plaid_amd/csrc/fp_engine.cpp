@@ -2179,7 +2179,7 @@ extern "C" int fp_kmeans(int device_id, const uint16_t* data, int64_t n, int32_t
                          uint64_t seed, float* out_centroids, int64_t* out_counts) {
   g_km_have = 0;
   if (!data || !init_rows || !out_centroids || n < 1 || k < 1 || niter < 0) return fail(FP_EINVAL, "bad argument");
-  if (dim < 1 || dim > 256) return fail(FP_EUNSUPPORTED, "fp_kmeans: dim must be in [1, 256]");
+  if (!assign_dim_accepted(dim)) return fail(FP_EUNSUPPORTED, "fp_kmeans: dim must be in [1, 256] or a multiple of 8 up to 1024");
   if (k > n) return fail(FP_EINVAL, "fp_kmeans: fewer training points (" + std::to_string(n) + ") than centroids (" + std::to_string(k) + ")");
   if (n >= 0x7FFFFFFFll) return fail(FP_EUNSUPPORTED, "fp_kmeans: more than 2^31-2 training points");
   for (int64_t c = 0; c < k; ++c)
@@ -2339,7 +2339,8 @@ extern "C" int fp_centroid_outliers(int device_id, const uint16_t* centroids, in
   *out_count = 0;
   if (!centroids || C < 1 || T < 0 || (T > 0 && (!emb || !out_rows))) return fail(FP_EINVAL, "bad argument");
   if (!(threshold_sq >= 0.f)) return fail(FP_EINVAL, "fp_centroid_outliers: threshold_sq must be a number >= 0");
-  if (dim < 1 || dim > 256) return fail(FP_EUNSUPPORTED, "fp_centroid_outliers: dim must be in [1, 256]");
+  if (!assign_dim_accepted(dim))
+    return fail(FP_EUNSUPPORTED, "fp_centroid_outliers: dim must be in [1, 256] or a multiple of 8 up to 1024");
   if (C >= 0x7FFFFFFFll) return fail(FP_EUNSUPPORTED, "too many centroids");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(FP_EHIP, "no HIP device available (this library has no CPU path)");

@@ -40,12 +40,15 @@ void fpk_km_scan_data(const uint16_t* data, int64_t n_elems, uint32_t* stat, hip
 //   cnt[c] == 0      cent32[c] = (float)data[mix64(stream_key(seed, 0x6B6D0000 + it) + c) % n]
 // then cent16 = RNE16(cent32) and hn[c] = 0.5f * the ascending-d fp32 chain of cent16[c][d]^2 (one lane walks it; a square of an
 // fp16 value is exact in fp32, so mul + add == fma).  stat = {max|cent16|, max hn} as fp32 bits (both >= 0: bit order = value order).
+// ROW = the floats a wave's LDS row holds: 256 serves dim <= 256 (1 KB per wave), 1024 every dim up to 1024 (4 waves x 4 KB =
+// 16 KB).  The loops stride a row by 64 lanes at any dim; the hn chain stays ONE lane walking the row in LDS, ascending d.
 #define KM_RESEED_STREAM 0x6B6D0000ull
+template <int ROW>
 __global__ __launch_bounds__(256) void k_km_finalise(const uint16_t* __restrict__ data, int64_t n, int D, int64_t K,
                                                      const int64_t* __restrict__ init_rows, const int64_t* __restrict__ sums,
                                                      const int32_t* __restrict__ cnt, uint64_t seed, int it, float* __restrict__ cent32,
                                                      uint16_t* __restrict__ cent16, float* __restrict__ half_sqnorm, uint32_t* __restrict__ stat) {
-  __shared__ float row[4][256];
+  __shared__ float row[4][ROW];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int64_t base = (int64_t)blockIdx.x * 4; base < K; base += (int64_t)gridDim.x * 4) {   // uniform over the workgroup
     const int64_t c = base + wave;
@@ -91,8 +94,12 @@ __global__ __launch_bounds__(256) void k_km_finalise(const uint16_t* __restrict_
 void fpk_km_finalise(const uint16_t* data, int64_t n, int D, int64_t K, const int64_t* init_rows, const int64_t* sums, const int32_t* cnt,
                      uint64_t seed, int it, float* cent32, uint16_t* cent16, float* half_sqnorm, uint32_t* stat, hipStream_t st) {
   (void)hipMemsetAsync(stat, 0, 8, st);
-  hipLaunchKernelGGL(k_km_finalise, dim3(fp_grid_cap((K + 3) / 4, 256)), dim3(256), 0, st, data, n, D, K, init_rows, sums, cnt, seed, it, cent32,
-                     cent16, half_sqnorm, stat);
+  const dim3 grid(fp_grid_cap((K + 3) / 4, 256));
+  if (D <= 256)
+    hipLaunchKernelGGL(k_km_finalise<256>, grid, dim3(256), 0, st, data, n, D, K, init_rows, sums, cnt, seed, it, cent32, cent16, half_sqnorm, stat);
+  else   // D <= 1024: the engine refuses anything larger
+    hipLaunchKernelGGL(k_km_finalise<1024>, grid, dim3(256), 0, st, data, n, D, K, init_rows, sums, cnt, seed, it, cent32, cent16, half_sqnorm,
+                       stat);
 }
 
 // ---- inverted index of the labels ---------------------------------------------------------------------------------------------
@@ -191,12 +198,100 @@ __global__ __launch_bounds__(256) void k_km_sum(const uint16_t* __restrict__ dat
     flush();
   }
 }
+// The same sums for a dim above 256 that is a multiple of 8 (U = D / 8 units of 16 bytes, U <= 128).  Lane l owns units l and,
+// with NU == 2 (U > 64), l + 64: every owned unit of a member is ONE 16-byte load, so a wave instruction reads a contiguous
+// kilobyte of the row (the kernel above: 128 bytes), and its eight halves feed eight int64 accumulators -- 8 * NU per lane, in
+// registers.  Slices, the hand-over of members and labels by lane shuffles and the flush on a cluster change are the kernel
+// above's; four members are loaded ahead of the adds (4 * NU loads of 16 bytes in flight per lane).  A unit that does not exist
+// (u >= U) issues no load and no atomic.  The flush adds to sums[c * D + 8 u + j]: 64-bit integer atomics, any order, same bits.
+// The whole row stays with one wave: a quarter row per wave would cut the accumulators to 8 * NU / 4 per lane but hand every
+// member and label round four times and flush in four places; the gfx950 build takes 64 / 94 VGPRs (NU 1 / 2), no scratch, 8 / 5
+// waves per SIMD, so the registers are not what limits it.
+template <int NU>
+__global__ __launch_bounds__(256) void k_km_sum_units(const uint16_t* __restrict__ data, int D, const int32_t* __restrict__ labels,
+                                                      const int32_t* __restrict__ members, int64_t total,
+                                                      unsigned long long* __restrict__ sums) {
+  const int lane = threadIdx.x & 63;
+  const int U = D >> 3;
+  const int64_t nslice = (total + KM_SLICE - 1) / KM_SLICE;
+  bool live[NU];
+#pragma unroll
+  for (int j = 0; j < NU; ++j) live[j] = lane + 64 * j < U;
+  for (int64_t sl = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); sl < nslice; sl += (int64_t)gridDim.x * 4) {
+    const int64_t p0 = sl * KM_SLICE;
+    const int cntp = total - p0 < KM_SLICE ? (int)(total - p0) : KM_SLICE;
+    int32_t mt[2], mc[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int q = h * 64 + lane;
+      mt[h] = q < cntp ? members[p0 + q] : 0;
+      mc[h] = q < cntp ? labels[mt[h]] : -1;
+    }
+    long long acc[NU][8];
+#pragma unroll
+    for (int j = 0; j < NU; ++j)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc[j][e] = 0;
+    int32_t cur = -1;
+    auto flush = [&]() {
+#pragma unroll
+      for (int j = 0; j < NU; ++j) {
+        if (cur >= 0 && live[j]) {
+          unsigned long long* dst = sums + (int64_t)cur * D + 8 * (lane + 64 * j);   // 8 (lane + 64 j) + e < 8 U = D
+#pragma unroll
+          for (int e = 0; e < 8; ++e)
+            if (acc[j][e] != 0) atomicAdd(dst + e, (unsigned long long)acc[j][e]);
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[j][e] = 0;
+      }
+    };
+    for (int i0 = 0; i0 < cntp; i0 += 4) {
+      int32_t c[4];
+      uint4 x[4][NU];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int i = i0 + u;   // < KM_SLICE: cntp <= KM_SLICE and i0 is a multiple of 4
+        const int32_t tt = __shfl(i < 64 ? mt[0] : mt[1], i & 63, 64);
+        const int32_t cc = __shfl(i < 64 ? mc[0] : mc[1], i & 63, 64);
+        c[u] = i < cntp ? cc : -1;
+#pragma unroll
+        for (int j = 0; j < NU; ++j)
+          x[u][j] = (c[u] >= 0 && live[j]) ? *reinterpret_cast<const uint4*>(data + (int64_t)tt * D + 8 * (lane + 64 * j)) : make_uint4(0, 0, 0, 0);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (c[u] < 0) continue;
+        if (c[u] != cur) {
+          flush();
+          cur = c[u];
+        }
+#pragma unroll
+        for (int j = 0; j < NU; ++j) {
+          const uint32_t w[4] = {x[u][j].x, x[u][j].y, x[u][j].z, x[u][j].w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            acc[j][2 * e] += fp_f16_fixed((uint16_t)(w[e] & 0xFFFFu));
+            acc[j][2 * e + 1] += fp_f16_fixed((uint16_t)(w[e] >> 16));
+          }
+        }
+      }
+    }
+    flush();
+  }
+}
 void fpk_km_sum(const uint16_t* data, int64_t n, int D, int64_t K, const int32_t* labels, const int32_t* members, int64_t* sums,
                 hipStream_t st) {
   (void)hipMemsetAsync(sums, 0, (size_t)K * D * 8, st);
   const int64_t nslice = (n + KM_SLICE - 1) / KM_SLICE;
-  hipLaunchKernelGGL(k_km_sum, dim3(fp_grid_cap((nslice + 3) / 4, 256)), dim3(256), 0, st, data, D, labels, members, n,
-                     reinterpret_cast<unsigned long long*>(sums));
+  const dim3 grid(fp_grid_cap((nslice + 3) / 4, 256));
+  unsigned long long* out = reinterpret_cast<unsigned long long*>(sums);
+  if (D <= 256)
+    hipLaunchKernelGGL(k_km_sum, grid, dim3(256), 0, st, data, D, labels, members, n, out);
+  else if (D <= 512)   // above 256 the engine admits multiples of 8 up to 1024 only: rows of whole, 16-byte aligned units
+    hipLaunchKernelGGL(k_km_sum_units<1>, grid, dim3(256), 0, st, data, D, labels, members, n, out);
+  else
+    hipLaunchKernelGGL(k_km_sum_units<2>, grid, dim3(256), 0, st, data, D, labels, members, n, out);
 }
 
 __global__ void k_km_widen_counts(const int32_t* __restrict__ in, int64_t* __restrict__ out, int64_t n) {

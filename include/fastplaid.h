@@ -296,14 +296,17 @@ int fp_assign_l2(int device_id, const uint16_t* centroids_f16 /*[n_centroids, di
  *      lowest c: what fp_assign_l2 returns for the same cent16 and hn (a dim that is a multiple of 8 with k >= 256 narrows the search
  *      with two MFMA passes, as fp_compress does, and re-checks the near-ties with that chain; the labels are the same)
  *   4. S[c][d] = the EXACT sum of data[t][d] over label[t] == c, cnt[c] the count.  Every finite fp16 value is an integer multiple
- *      of 2^-24; the sums are int64 integers in that unit, so they do not depend on the order of the additions
+ *      of 2^-24; the sums are int64 integers in that unit, so they do not depend on the order of the additions.  Above dim 256 a
+ *      row is read as dim / 8 units of 16 bytes (a lane owns units l and l + 64, eight int64 accumulators per unit); the partial
+ *      sums still meet in 64-bit integer atomics only
  *   5. cnt[c] > 0:  cent32[c][d] = (float)(((double)S_int * 2^-24) / (double)cnt[c]), every step round to nearest even
  *   6. cnt[c] == 0: cent32[c] = (float)data[r], r = rnd(seed, 0x6B6D0000 + it, c) % n with the splitmix64 counter hash of the
  *      synthetic generator (synth.rnd): mix64(mix64(seed * 0xD1342543DE82EF95 + stream) + counter)
  * out_centroids [k, dim] f32 = cent32 after the last iteration (niter == 0: the initial rows); out_counts [k] (nullable) = cnt of
  * the last assignment, all zero when niter == 0.  L2-normalisation and the cast to fp16 are the caller's (kmeans.compute_kmeans).
- * Errors: FP_EINVAL for a value that is not finite, k > n, an init_rows entry outside [0, n); FP_EUNSUPPORTED for dim outside
- * [1, 256], n >= 2^31-1, or n * max|x| * 2^24 >= 2^62 (max|x| is taken on the device; beyond it an int64 sum could overflow);
+ * dim as fp_compress: 1 .. 256, or a multiple of 8 up to 1024.
+ * Errors: FP_EINVAL for a value that is not finite, k > n, an init_rows entry outside [0, n); FP_EUNSUPPORTED for a dim that is
+ * neither in [1, 256] nor a multiple of 8 up to 1024, n >= 2^31-1, or n * max|x| * 2^24 >= 2^62 (max|x| is taken on the device; beyond it an int64 sum could overflow);
  * FP_ENOMEM when the sample and its work buffers do not fit the device. */
 int fp_kmeans(int device_id, const uint16_t* data_f16 /*[n, dim]*/, int64_t n, int32_t dim, int64_t k, int32_t niter,
               const int64_t* init_rows /*[k]*/, uint64_t seed, float* out_centroids /*[k, dim]*/, int64_t* out_counts /*[k] or NULL*/);
@@ -330,7 +333,9 @@ int fp_kmeans_last_timings(float* ms, int cap);
  * [n_tokens] are optional.  The compaction is ordered (per-tile counts -> scan -> write): nothing depends on scheduling, and
  * there is no float atomic.  n_tokens == 0 succeeds with *out_count = 0.
  * Errors: FP_EINVAL for n_centroids < 1, a negative size, a NaN or negative threshold_sq, a centroid or embedding value that is
- * not finite (checked on the device); FP_EUNSUPPORTED for dim outside [1, 256]; FP_ENOMEM / FP_EHIP from the runtime. */
+ * not finite (checked on the device); FP_EUNSUPPORTED for a dim that is neither in [1, 256] nor a multiple of 8 up to 1024 (above
+ * 256 the chains of hn, x . c and x2 read their rows from 64-dim slices staged in LDS: the same order, the same bits); FP_ENOMEM /
+ * FP_EHIP from the runtime. */
 int fp_centroid_outliers(int device_id, const uint16_t* centroids_f16 /*[n_centroids, dim]*/, int64_t n_centroids, int32_t dim,
                          const uint16_t* embeddings_f16 /*[n_tokens, dim]*/, int64_t n_tokens, float threshold_sq,
                          int64_t* out_rows /*[n_tokens] capacity*/, int64_t* out_count, float* out_sqdist /*[n_tokens] or NULL*/,

@@ -8,6 +8,7 @@ One run = one path at one shape (run them one at a time, each under its own time
 
     python tools/bench_kmeans.py --shape small --path host        n = 2^21, k = 2^13, dim 128
     python tools/bench_kmeans.py --shape large --path native      n = 2^23, k = 2^16, dim 128
+    python tools/bench_kmeans.py --shape small --dim 768 --path native      the same n and k at another dim
 
 Prints one JSON line: wall seconds of the call (after a tiny warm-up call that loads the library and the device), and for the native
 path the HIP-event split of the device time (upload / assign / index / sum / finalise, summed over the iterations)."""
@@ -44,9 +45,11 @@ def main():
     ap.add_argument("--path", choices=["host", "native"], required=True)
     ap.add_argument("--niter", type=int, default=4)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--dim", type=int, default=None, help="instead of the shape's dim (1 .. 256, or a multiple of 8 up to 1024)")
     args = ap.parse_args()
     from fast_plaid_amd import kmeans
     n, k, dim = SHAPES[args.shape]
+    dim = args.dim or dim
     t0 = time.perf_counter()
     data = sample(n, k, dim, args.seed)
     t_gen = time.perf_counter() - t0

@@ -10,6 +10,7 @@ One run = both paths at one shape, one after the other in one process (the same 
 
     python tools/bench_outliers.py --shape small      2^20 tokens x 2^13 centroids, dim 128
     python tools/bench_outliers.py --shape large      2^22 tokens x 2^16 centroids, dim 128
+    python tools/bench_outliers.py --shape small --dim 1024 --skip-host      another dim, the native path alone (A/B runs of it)
 
 Prints one JSON line: wall seconds of each path (after a tiny warm-up call that loads the library and the device), the outlier
 counts of both, and for the native path the HIP-event split of its device time (upload + data check / assignment / distance +
@@ -66,31 +67,38 @@ def main():
     ap.add_argument("--shape", choices=sorted(SHAPES), required=True)
     ap.add_argument("--threshold", type=float, default=0.5)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--dim", type=int, default=None, help="instead of the shape's dim (1 .. 256, or a multiple of 8 up to 1024)")
+    ap.add_argument("--skip-host", action="store_true", help="the native path alone: no host wall time, speed-up or row comparison")
     args = ap.parse_args()
     from fast_plaid_amd import maintain
     n, c, dim = SHAPES[args.shape]
+    dim = args.dim or dim
     t0 = time.perf_counter()
     cent, emb = sample(n, c, dim, args.seed)
     t_gen = time.perf_counter() - t0
     maintain.centroid_outliers(cent[:256], emb[:2048], args.threshold, rows_only=True)
-    host_route(cent[:256], emb[:2048], args.threshold)
+    if not args.skip_host:
+        host_route(cent[:256], emb[:2048], args.threshold)
     t0 = time.perf_counter()
     rows, _, _ = maintain.centroid_outliers(cent, emb, args.threshold, rows_only=True)
     wall_native = time.perf_counter() - t0
     counts = maintain.last_outlier_counts()
-    t0 = time.perf_counter()
-    rows_host = host_route(cent, emb, args.threshold)
-    wall_host = time.perf_counter() - t0
+    rows_host, wall_host = None, None
+    if not args.skip_host:
+        t0 = time.perf_counter()
+        rows_host = host_route(cent, emb, args.threshold)
+        wall_host = time.perf_counter() - t0
     dev = {k: round(counts[k] / 1000.0, 3) for k in ("upload_us", "assign_us", "outlier_us", "download_us")}
     res = dict(tool="bench_outliers", shape=args.shape, n=n, c=c, dim=dim, threshold=args.threshold, seed=args.seed, gen_s=round(t_gen, 2),
-               native_wall_s=round(wall_native, 4), host_wall_s=round(wall_host, 4), speedup=round(wall_host / wall_native, 2),
-               outliers_native=int(rows.shape[0]), outliers_host=int(rows_host.shape[0]),
-               rows_only_in_one=int(np.setxor1d(rows, rows_host).shape[0]),   # numpy's distance rounds elsewhere: the edge may differ
+               native_wall_s=round(wall_native, 4), outliers_native=int(rows.shape[0]), rows_digest=int(rows.sum() % (1 << 61)),
                chunks=counts["chunks"], narrowed_chunks=counts["narrowed_chunks"], fallback_chunks=counts["fallback_chunks"],
                device_ms={k[:-3]: v for k, v in dev.items()},
                device_ms_per_chunk={k[:-3]: round(v / max(counts["chunks"], 1), 3) for k, v in dev.items()},
                share_of_wall={k[:-3]: round(v / 1000.0 / wall_native, 4) for k, v in dev.items()},
                assign_ns_per_point=round(counts["assign_us"] * 1000.0 / n, 2))
+    if rows_host is not None:
+        res.update(host_wall_s=round(wall_host, 4), speedup=round(wall_host / wall_native, 2), outliers_host=int(rows_host.shape[0]),
+                   rows_only_in_one=int(np.setxor1d(rows, rows_host).shape[0]))   # numpy's distance rounds elsewhere: the edge may differ
     print(json.dumps(res))
 
 
