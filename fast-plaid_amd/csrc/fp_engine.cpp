@@ -2,6 +2,8 @@
 // Replaces, for the search path, rust/search/{search,load,tensor,padding}.rs and
 // rust/utils/residual_codec.rs of the reference: index construction = upload + re-layout,
 // search_many = one batched, stream-ordered pipeline of HIP kernels (fp_kernels.hip, fp_maxsim.hip).
+// The stand-alone index-build operators (fp_compress, fp_assign_l2, fp_kmeans, fp_centroid_outliers) are in fp_build.cpp; what
+// the two files share is declared in fp_host.h and defined here.
 // No torch / tch; only the HIP runtime.
 #include <atomic>
 #include "../../include/fastplaid.h"
@@ -14,22 +16,17 @@
 #include <string>
 #include <vector>
 
+#include "fp_host.h"
 #include "fp_internal.h"
 
 // ------------------------------------------------------------------------------------------
 // errors (rust/utils/errors.rs:5-7: every failure becomes one message string)
 // ------------------------------------------------------------------------------------------
 static thread_local std::string g_err;
-static int fail(int code, const std::string& msg) {
+int fp_fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
-#define HIPCHK(x)                                                                                      \
-  do {                                                                                                 \
-    hipError_t e_ = (x);                                                                               \
-    if (e_ != hipSuccess)                                                                              \
-      return fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e_) + " at " #x);            \
-  } while (0)
 
 // a kernel launch reports a bad configuration only through hipGetLastError: every stage boundary checks it, so a failed launch
 // stops the search with the stage named instead of surfacing later in somebody else's HIP call
@@ -37,13 +34,13 @@ static int fail(int code, const std::string& msg) {
   do {                                                                                                 \
     hipError_t l_ = hipGetLastError();                                                                 \
     if (l_ != hipSuccess)                                                                              \
-      return fail(FP_EHIP, std::string("HIP launch error: ") + hipGetErrorString(l_) + " before the end of stage " #X); \
+      return fp_fail(FP_EHIP, std::string("HIP launch error: ") + hipGetErrorString(l_) + " before the end of stage " #X); \
     if (!s->capturing) HIPCHK(hipEventRecord(s->ev[X], st));                                           \
   } while (0)
 #define LAUNCHCHK(where)                                                                               \
   do {                                                                                                 \
     hipError_t l_ = hipGetLastError();                                                                 \
-    if (l_ != hipSuccess) return fail(FP_EHIP, std::string("HIP launch error: ") + hipGetErrorString(l_) + " in " where); \
+    if (l_ != hipSuccess) return fp_fail(FP_EHIP, std::string("HIP launch error: ") + hipGetErrorString(l_) + " in " where); \
   } while (0)
 
 extern "C" const char* fp_last_error(void) { return g_err.c_str(); }
@@ -109,7 +106,7 @@ struct DevBuf {
 // capture is open, and one refused call invalidates the capture: two threads searching one index failed each other's calls
 // (found by tests/fuzz_worker.py threads, round 6).  Relaxed means what the library needs: its captures concern the capturing
 // stream only.
-static hipError_t fp_set_device(int device) {
+hipError_t fp_set_device(int device) {
   static thread_local bool relaxed = false;
   if (!relaxed) {
     hipStreamCaptureMode m = hipStreamCaptureModeRelaxed;
@@ -455,8 +452,8 @@ static int upload_narrow(const int64_t* host, int32_t* dev, int64_t n, hipStream
   }
   if (e == hipSuccess && bad) e = copy_sync(&h_bad, bad, 4, hipMemcpyDeviceToHost, st);
   (void)hipFree(stage);
-  if (e != hipSuccess) return fail(FP_EHIP, hipGetErrorString(e));
-  if (h_bad) return fail(FP_EINVAL, std::string(what) + ": " + std::to_string(h_bad) + " entries outside [0, " + std::to_string(limit) + ")");
+  if (e != hipSuccess) return fp_fail(FP_EHIP, hipGetErrorString(e));
+  if (h_bad) return fp_fail(FP_EINVAL, std::string(what) + ": " + std::to_string(h_bad) + " entries outside [0, " + std::to_string(limit) + ")");
   return FP_OK;
 }
 
@@ -464,8 +461,8 @@ static int upload_narrow(const int64_t* host, int32_t* dev, int64_t n, hipStream
 // 8-dim (16-byte) pieces, hence dim % 8.  Every accepted shape has an MFMA MaxSim kernel: fixed-dim ones for thirteen shapes
 // (k_maxsim6 / k_maxsim5), the K-sliced k_maxsim_sl at a runtime dim for the rest.
 static int check_shape(int nbits, int dim) {
-  if (!(nbits == 1 || nbits == 2 || nbits == 4 || nbits == 8)) return fail(FP_EINVAL, "nbits must divide 8 (1, 2, 4 or 8)");
-  if (dim < 8 || dim % 8 != 0 || dim > 1024) return fail(FP_EUNSUPPORTED, "dim must be a multiple of 8 in [8, 1024]");
+  if (!(nbits == 1 || nbits == 2 || nbits == 4 || nbits == 8)) return fp_fail(FP_EINVAL, "nbits must divide 8 (1, 2, 4 or 8)");
+  if (dim < 8 || dim % 8 != 0 || dim > 1024) return fp_fail(FP_EUNSUPPORTED, "dim must be a multiple of 8 in [8, 1024]");
   return FP_OK;
 }
 
@@ -494,18 +491,18 @@ static int finish_layout(fp_index* ix, int maxlen, hipStream_t st) {
     uint16_t* perm = nullptr;
     const int src = fps_sort_docs(const_cast<int32_t*>(D.codes), const_cast<uint8_t*>(D.residuals), D.doc_off, D.N, D.T, maxlen, D.pr, &perm, st);
     if (perm) { ix->owned.push_back(perm); ix->bytes += D.T * 2; }
-    if (src != 0) return fail(FP_EHIP, "in-document token sort failed (hip error " + std::to_string(src) + ")");
+    if (src != 0) return fp_fail(FP_EHIP, "in-document token sort failed (hip error " + std::to_string(src) + ")");
     D.perm = perm;
   }
   {
     uint16_t* norms = nullptr;
     hipError_t e = hipMalloc((void**)&norms, (size_t)std::max<int64_t>(D.T, 1) * 2 + 64);
-    if (e != hipSuccess) return fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e) + " (token norms)");
+    if (e != hipSuccess) return fp_fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e) + " (token norms)");
     ix->owned.push_back(norms);
     ix->bytes += D.T * 2;
     fpk_token_norms(D, norms, st);
     e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e) + " (token norms)");
+    if (e != hipSuccess) return fp_fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e) + " (token norms)");
     D.norms = norms;
   }
   // S1's zero-padded view of the centroid table (FpIndexDev::cent_s1)
@@ -515,13 +512,13 @@ static int finish_layout(fp_index* ix, int maxlen, hipStream_t st) {
     const int dp = D.dim < 64 ? 64 : (D.dim < 128 ? 128 : 256);
     uint16_t* cp = nullptr;
     hipError_t e = hipMalloc((void**)&cp, (size_t)D.C * dp * 2 + 64);
-    if (e != hipSuccess) return fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e) + " (padded centroid table)");
+    if (e != hipSuccess) return fp_fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e) + " (padded centroid table)");
     ix->owned.push_back(cp);
     ix->bytes += D.C * dp * 2;
     e = hipMemsetAsync(cp, 0, (size_t)D.C * dp * 2, st);
     if (e == hipSuccess) e = hipMemcpy2DAsync(cp, (size_t)dp * 2, D.centroids, (size_t)D.dim * 2, (size_t)D.dim * 2, (size_t)D.C, hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e) + " (padded centroid table)");
+    if (e != hipSuccess) return fp_fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e) + " (padded centroid table)");
     D.cent_s1 = cp;
     D.dim_s1 = dp;
   }
@@ -536,18 +533,18 @@ static int finish_layout(fp_index* ix, int maxlen, hipStream_t st) {
       uint32_t* rv = nullptr;
       unsigned long long* nh = nullptr;
       e = hipMalloc((void**)&rv, (size_t)std::max<int64_t>(D.T, 1) * 4 + 64);
-      if (e != hipSuccess) return fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e) + " (token reciprocals)");
+      if (e != hipSuccess) return fp_fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e) + " (token reciprocals)");
       ix->owned.push_back(rv);
       ix->bytes += D.T * 4;
       e = hipMalloc((void**)&nh, 8);
-      if (e != hipSuccess) return fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e) + " (token reciprocals)");
+      if (e != hipSuccess) return fp_fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e) + " (token reciprocals)");
       ix->owned.push_back(nh);
       (void)hipMemsetAsync(nh, 0, 8, st);
       fpk_token_rinv(D, rv, nh, st);
       unsigned long long hard = 0;
       e = hipMemcpyAsync(&hard, nh, 8, hipMemcpyDeviceToHost, st);
       if (e == hipSuccess) e = hipStreamSynchronize(st);
-      if (e != hipSuccess) return fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e) + " (token reciprocals)");
+      if (e != hipSuccess) return fp_fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e) + " (token reciprocals)");
       D.rinv = rv;
       ix->n_hard_tokens = (int64_t)hard;
     }
@@ -555,23 +552,23 @@ static int finish_layout(fp_index* ix, int maxlen, hipStream_t st) {
       const int64_t slab = std::max<int64_t>(1, std::min<int64_t>(D.T, (512ll << 20) / D.pr));
       uint8_t* tmp = nullptr;
       e = hipMalloc((void**)&tmp, (size_t)slab * D.pr);
-      if (e != hipSuccess) return fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e) + " (native residual order)");
+      if (e != hipSuccess) return fp_fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e) + " (native residual order)");
       for (int64_t t0 = 0; t0 < D.T; t0 += slab) fpk_resid_native(D, t0, std::min<int64_t>(slab, D.T - t0), tmp, st);
       e = hipStreamSynchronize(st);
       (void)hipFree(tmp);
-      if (e != hipSuccess) return fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e) + " (native residual order)");
+      if (e != hipSuccess) return fp_fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e) + " (native residual order)");
     }
     D.resid_native = 1;
   }
   {
     int64_t* uoff = nullptr; int32_t* ucodes = nullptr; int64_t U = 0;
     hipError_t e = hipMalloc((void**)&uoff, ((size_t)D.N + 1) * 8 + 64);
-    if (e != hipSuccess) return fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e) + " (unique-code offsets)");
+    if (e != hipSuccess) return fp_fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e) + " (unique-code offsets)");
     ix->owned.push_back(uoff);
     ix->bytes += (D.N + 1) * 8;
     const int urc = fps_build_ucodes(D.codes, D.doc_off, D.N, maxlen, &ucodes, &U, uoff, st);
     if (ucodes) { ix->owned.push_back(ucodes); ix->bytes += U * 4; }
-    if (urc != 0) return fail(FP_EHIP, "unique-code build failed (hip error " + std::to_string(urc) + ")");
+    if (urc != 0) return fp_fail(FP_EHIP, "unique-code build failed (hip error " + std::to_string(urc) + ")");
     D.ucodes = ucodes; D.uoff = uoff; D.U = U;
   }
   // packed code lines for S4's level 0: one set per range of 2^17 centroids (codes relative to the range), up to 2^20
@@ -592,7 +589,7 @@ static int finish_layout(fp_index* ix, int maxlen, hipStream_t st) {
     void* shared = nullptr;
     if (nr > 1) {
       const size_t sb = (size_t)D.N * nr * 16 * D.l0_ppl + 256;
-      if (hipMalloc(&shared, sb) != hipSuccess) return fail(FP_EHIP, "packed-code build failed (out of memory)");
+      if (hipMalloc(&shared, sb) != hipSuccess) return fp_fail(FP_EHIP, "packed-code build failed (out of memory)");
       ix->owned.push_back(shared);
       ix->bytes += (int64_t)sb;
       D.n_lines += D.N * nr;
@@ -603,7 +600,7 @@ static int finish_layout(fp_index* ix, int maxlen, hipStream_t st) {
       const int prc = fps_build_pcodes(D.ucodes, D.uoff, D.N, lo, hi, &lines, &poff, &nl, st, D.l0_ppl, D.C, shared, nr, r);
       if (lines) { ix->owned.push_back(lines); ix->bytes += nl * 16 * D.l0_ppl; D.n_lines += nl; }
       if (poff) { ix->owned.push_back(poff); ix->bytes += (D.N + 1) * 8; }
-      if (prc != 0) return fail(FP_EHIP, "packed-code build failed (hip error " + std::to_string(prc) + ")");
+      if (prc != 0) return fp_fail(FP_EHIP, "packed-code build failed (hip error " + std::to_string(prc) + ")");
       D.pcodes_r[r] = static_cast<const uint4*>(lines); D.poff_r[r] = poff;
     }
     D.n_ranges = nr;
@@ -613,13 +610,13 @@ static int finish_layout(fp_index* ix, int maxlen, hipStream_t st) {
 }
 
 extern "C" int fp_index_create(const fp_index_desc* d, int device_id, fp_index** out) {
-  if (!d || !out) return fail(FP_EINVAL, "null argument");
+  if (!d || !out) return fp_fail(FP_EINVAL, "null argument");
   *out = nullptr;
   if (int rc = check_shape(d->nbits, d->dim)) return rc;
-  if (d->n_centroids <= 0 || !d->centroids || !d->bucket_weights) return fail(FP_EINVAL, "centroids / bucket_weights missing");
+  if (d->n_centroids <= 0 || !d->centroids || !d->bucket_weights) return fp_fail(FP_EINVAL, "centroids / bucket_weights missing");
   if (d->n_docs < 0 || (d->n_docs > 0 && (!d->doc_lengths || !d->doc_codes || !d->doc_residuals)))
-    return fail(FP_EINVAL, "document arrays missing");
-  if (d->n_docs >= 0x7FFFFFFFll) return fail(FP_EUNSUPPORTED, "more than 2^31-1 documents per index shard");
+    return fp_fail(FP_EINVAL, "document arrays missing");
+  if (d->n_docs >= 0x7FFFFFFFll) return fp_fail(FP_EUNSUPPORTED, "more than 2^31-1 documents per index shard");
   HIPCHK(fp_set_device(device_id));
   fp_index* ix = new fp_index();
   ix->device = device_id;
@@ -637,7 +634,7 @@ extern "C" int fp_index_create(const fp_index_desc* d, int device_id, fp_index**
   int maxlen = 0;
   for (int64_t i = 0; i < D.N; ++i) {
     int64_t l = d->doc_lengths[i];
-    if (l < 0) return bail(fail(FP_EINVAL, "negative document length"));
+    if (l < 0) return bail(fp_fail(FP_EINVAL, "negative document length"));
     ix->h_doc_off[i + 1] = ix->h_doc_off[i] + l;
     if (l > maxlen) maxlen = (int)l;
   }
@@ -645,7 +642,7 @@ extern "C" int fp_index_create(const fp_index_desc* d, int device_id, fp_index**
   D.max_doc_len = maxlen;
   uint16_t* cent = nullptr; uint16_t* lut = nullptr; int64_t* doc_off = nullptr; int32_t* codes = nullptr; uint8_t* res = nullptr;
   int64_t* ivf_off = nullptr; int32_t* ivf_pids = nullptr;
-#define ICHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return bail(fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e_) + " at " #x)); } while (0)
+#define ICHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return bail(fp_fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e_) + " at " #x)); } while (0)
   ICHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
   ICHK(dev_alloc(ix, &cent, (size_t)D.C * D.dim));
   ICHK(copy_sync(cent, d->centroids, (size_t)D.C * D.dim * 2, hipMemcpyHostToDevice, st));
@@ -667,7 +664,7 @@ extern "C" int fp_index_create(const fp_index_desc* d, int device_id, fp_index**
   {
     std::vector<int64_t> hoff((size_t)D.P + 1, 0);
     for (int64_t i = 0; i < D.P; ++i) {
-      if (d->ivf_lengths[i] < 0) return bail(fail(FP_EINVAL, "negative ivf length"));
+      if (d->ivf_lengths[i] < 0) return bail(fp_fail(FP_EINVAL, "negative ivf length"));
       hoff[i + 1] = hoff[i] + d->ivf_lengths[i];
     }
     ICHK(dev_alloc(ix, &ivf_off, hoff.size()));
@@ -740,12 +737,12 @@ extern "C" int32_t fp_index_tickets_ok(const fp_index* ix) { return ix && ix->ti
 // synthetic device-resident corpora
 // ------------------------------------------------------------------------------------------
 extern "C" int fp_index_create_synthetic(const fp_synth_desc* d, int device_id, fp_index** out) {
-  if (!d || !out) return fail(FP_EINVAL, "null argument");
+  if (!d || !out) return fp_fail(FP_EINVAL, "null argument");
   *out = nullptr;
   if (int rc = check_shape(d->nbits, d->dim)) return rc;
-  if (d->n_centroids <= 1 || (d->n_centroids & (d->n_centroids - 1))) return fail(FP_EINVAL, "n_centroids must be a power of two");
-  if (d->doc_begin < 0 || d->doc_end < d->doc_begin || d->doc_end > d->n_docs_total) return fail(FP_EINVAL, "bad document range");
-  if (d->doc_len < 1) return fail(FP_EINVAL, "doc_len < 1");
+  if (d->n_centroids <= 1 || (d->n_centroids & (d->n_centroids - 1))) return fp_fail(FP_EINVAL, "n_centroids must be a power of two");
+  if (d->doc_begin < 0 || d->doc_end < d->doc_begin || d->doc_end > d->n_docs_total) return fp_fail(FP_EINVAL, "bad document range");
+  if (d->doc_len < 1) return fp_fail(FP_EINVAL, "doc_len < 1");
   HIPCHK(fp_set_device(device_id));
   fp_index* ix = new fp_index();
   ix->device = device_id;
@@ -768,7 +765,7 @@ extern "C" int fp_index_create_synthetic(const fp_synth_desc* d, int device_id, 
   const int64_t tok_base = hoff[(size_t)D.N + 1];
   D.max_doc_len = maxlen;
   ix->h_doc_off.assign(hoff.begin(), hoff.begin() + D.N + 1);
-#define ICHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return bail(fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e_) + " at " #x)); } while (0)
+#define ICHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return bail(fp_fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e_) + " at " #x)); } while (0)
   uint16_t* cent = nullptr; uint16_t* lut = nullptr; int64_t* doc_off = nullptr; int32_t* codes = nullptr; uint8_t* res = nullptr;
   int64_t* ivf_off = nullptr; int32_t* ivf_pids = nullptr;
   StreamGuard sg;
@@ -793,7 +790,7 @@ extern "C" int fp_index_create_synthetic(const fp_synth_desc* d, int device_id, 
   int64_t tot = 0;
   int rc = fps_build_ivf(D.ucodes, D.uoff, D.N, D.U, D.P, &ivf_pids, &tot, ivf_off, st);
   if (ivf_pids) { ix->owned.push_back(ivf_pids); ix->bytes += tot * 4; }
-  if (rc != 0) return bail(fail(FP_EHIP, "IVF build failed (hip/hipcub error " + std::to_string(rc) + ")"));
+  if (rc != 0) return bail(fp_fail(FP_EHIP, "IVF build failed (hip/hipcub error " + std::to_string(rc) + ")"));
   ICHK(hipStreamSynchronize(st));
 #undef ICHK
   ix->has_ivf = true;
@@ -812,10 +809,10 @@ static inline void row_to_reference_order(const fp_index* ix, const uint8_t* sto
 }
 
 extern "C" int64_t fp_index_read_doc(const fp_index* ix, int64_t doc, int64_t* codes, uint8_t* residuals, int64_t cap) {
-  if (!ix || doc < 0 || doc >= ix->d.N) return fail(FP_EINVAL, "bad document id");
+  if (!ix || doc < 0 || doc >= ix->d.N) return fp_fail(FP_EINVAL, "bad document id");
   (void)fp_set_device(ix->device);
   const int64_t off = ix->h_doc_off[doc], len = ix->h_doc_off[doc + 1] - off;
-  if (len > cap) return fail(FP_EINVAL, "capacity too small");
+  if (len > cap) return fp_fail(FP_EINVAL, "capacity too small");
   const int pr = ix->d.pr;
   std::vector<int32_t> tmp((size_t)len);
   std::vector<uint8_t> rtmp((size_t)len * pr);
@@ -834,12 +831,12 @@ extern "C" int64_t fp_index_read_doc(const fp_index* ix, int64_t doc, int64_t* c
 }
 
 extern "C" int64_t fp_index_read_ivf(const fp_index* ix, int64_t cell, int64_t* pids, int64_t cap) {
-  if (!ix || !ix->has_ivf || cell < 0 || cell >= ix->d.P) return fail(FP_EINVAL, "bad cell");
+  if (!ix || !ix->has_ivf || cell < 0 || cell >= ix->d.P) return fp_fail(FP_EINVAL, "bad cell");
   (void)fp_set_device(ix->device);
   int64_t be[2];
   HIPCHK(copy_sync(be, ix->d.ivf_off + cell, 16, hipMemcpyDeviceToHost, util_stream(ix->device)));
   const int64_t len = be[1] - be[0];
-  if (len > cap) return fail(FP_EINVAL, "capacity too small");
+  if (len > cap) return fp_fail(FP_EINVAL, "capacity too small");
   std::vector<int32_t> tmp((size_t)len);
   if (len > 0) HIPCHK(copy_sync(tmp.data(), ix->d.ivf_pids + be[0], (size_t)len * 4, hipMemcpyDeviceToHost, util_stream(ix->device)));
   for (int64_t i = 0; i < len; ++i) pids[i] = tmp[i];
@@ -854,16 +851,16 @@ struct TraceOut {
 };
 
 static int validate_search(const fp_index* ix, int32_t nq, int32_t q_len, int32_t dim, const fp_search_params* p) {
-  if (!ix || !p) return fail(FP_EINVAL, "null argument");
+  if (!ix || !p) return fp_fail(FP_EINVAL, "null argument");
   if (!ix->has_ivf)  // search.rs:227-232
-    return fail(FP_ECOMPRESS_ONLY,
+    return fp_fail(FP_ECOMPRESS_ONLY,
                 "This index was built with compress_only=True and does not support search. Rebuild with compress_only=False "
                 "to enable search.");
-  if (nq < 0 || q_len < 1) return fail(FP_EINVAL, "Expected a 3D tensor for queries with at least one token per query");
-  if (dim != ix->d.dim) return fail(FP_EINVAL, "query dim does not match the index dim");
-  if (p->top_k < 0 || p->n_full_scores < 0 || p->n_ivf_probe < 0) return fail(FP_EINVAL, "negative search parameter");
-  if ((int64_t)q_len * std::max<int64_t>(p->n_ivf_probe, 1) > (1ll << 28)) return fail(FP_EUNSUPPORTED, "q_len * n_ivf_probe > 2^28");
-  if (p->n_full_scores / 4 > (1ll << 24)) return fail(FP_EUNSUPPORTED, "n_full_scores > 2^26");
+  if (nq < 0 || q_len < 1) return fp_fail(FP_EINVAL, "Expected a 3D tensor for queries with at least one token per query");
+  if (dim != ix->d.dim) return fp_fail(FP_EINVAL, "query dim does not match the index dim");
+  if (p->top_k < 0 || p->n_full_scores < 0 || p->n_ivf_probe < 0) return fp_fail(FP_EINVAL, "negative search parameter");
+  if ((int64_t)q_len * std::max<int64_t>(p->n_ivf_probe, 1) > (1ll << 28)) return fp_fail(FP_EUNSUPPORTED, "q_len * n_ivf_probe > 2^28");
+  if (p->n_full_scores / 4 > (1ll << 24)) return fp_fail(FP_EUNSUPPORTED, "n_full_scores > 2^26");
   return FP_OK;
 }
 
@@ -1042,7 +1039,7 @@ static int run_front(Pipe& P, const int64_t* h_sub_ids, const int64_t* h_sub_off
     HIPCHK(s->l0_e8.ensure((size_t)B * Cpad));
     HIPCHK(s->l0_esc.ensure((size_t)B * 64 * 4));
     if (fpk_centroid_scores(D1, q_s1, s->Ssample.as<uint16_t>(), B, sh.Qp, s->S8.as<uint8_t>(), nullptr, st, ns, sstride))
-      return fail(FP_EUNSUPPORTED, "dim");
+      return fp_fail(FP_EUNSUPPORTED, "dim");
     HIPCHK(s->l0_gfl.ensure((size_t)B * sh.Qp * 2));
     static const int s1_rd = fp_test_opt("s1_rd", 1) != 0 ? 1 : 0;   // the epilogue's one-fma form of the excess (0: the floor / clamp / subtract form, for A/B runs)
     fpk_l0_floors(s->S8.as<uint8_t>(), ns, sh, s->l0_floors.as<uint8_t>(), s->l0_F.as<uint32_t>(), s->l0_esc.as<uint32_t>(), s->l0_gfl.as<uint16_t>(), st,
@@ -1052,13 +1049,13 @@ static int run_front(Pipe& P, const int64_t* h_sub_ids, const int64_t* h_sub_off
     FpS1Excess ex{s->l0_floors.as<uint8_t>(), s->l0_gfl.as<uint16_t>(), s->l0_e8.as<uint8_t>(), s->l0_esc.as<uint32_t>(), Cpad, sh.Q, s1_rd};
     STAGE_DONE(ST_S1MAIN);
     if (fpk_centroid_scores(D1, q_s1, s->S.as<uint16_t>(), B, sh.Qp, nullptr, s->cmax128.as<uint16_t>(), st, 0, 1, &ex, &xe))
-      return fail(FP_EUNSUPPORTED, "dim");
+      return fp_fail(FP_EUNSUPPORTED, "dim");
   } else {
     if (want_s8) HIPCHK(s->S8.ensure((size_t)B * D.C * sh.Qp));
     STAGE_DONE(ST_S1MAIN);
     if (fpk_centroid_scores(D1, q_s1, s->S.as<uint16_t>(), B, sh.Qp, want_s8 ? s->S8.as<uint8_t>() : nullptr,
                             s->cmax128.as<uint16_t>(), st, 0, 1, nullptr, &xe))
-      return fail(FP_EUNSUPPORTED, "dim");
+      return fp_fail(FP_EUNSUPPORTED, "dim");
   }
   STAGE_DONE(ST_PROBE);
   // subset bitmaps
@@ -1090,7 +1087,7 @@ static int run_front(Pipe& P, const int64_t* h_sub_ids, const int64_t* h_sub_off
     if (fpk_probe(D, s->S.as<uint16_t>(), sh, has_subset ? s->allow.as<uint32_t>() : nullptr, s->partial.as<unsigned long long>(),
                   P.nchunk, s->cells.as<int32_t>(), s->ucells.as<int32_t>(), s->ncells.as<int32_t>(), s->cmax128.as<uint16_t>(), st,
                   P.probe_prezeroed, !P.probe_no_fb, P.s1_mode != 0 ? &xe : nullptr, lz))
-      return fail(FP_EUNSUPPORTED, "n_ivf_probe");
+      return fp_fail(FP_EUNSUPPORTED, "n_ivf_probe");
   } else {
     HIPCHK(hipMemsetAsync(s->ncells.p, 0, (size_t)B * 4, st));  // topk(0) -> no cells -> empty result
   }
@@ -1260,7 +1257,7 @@ static int run_front(Pipe& P, const int64_t* h_sub_ids, const int64_t* h_sub_off
                46 vs 53 us, B = 64 90 vs 71 us)*/ !lz && B <= 16 && sh.R <= FP_MAX_SORT && (P.approx_impl != 0 || M <= 16384ll * B),
              P.selhist_prezeroed, s->ms_pref.as<int64_t>(), lz, &D,
              /*list length per query: the bound stages leave a few x R survivors, otherwise every candidate*/ sel_src != s->cand_pid.as<int32_t>() ? 8 * sh.R : (B > 0 ? M / B : 0)))
-    return fail(FP_EINVAL, "internal: the lazy selection was asked for on a shape it does not serve");
+    return fp_fail(FP_EINVAL, "internal: the lazy selection was asked for on a shape it does not serve");
   if (lz && !s->fold_stats)   // device-resident I/O: the overflow flag travels by itself (host-buffer calls: with the result block)
     HIPCHK(hipMemcpyAsync(static_cast<char*>(s->h_small.p) + 40, lz->flag, 4, hipMemcpyDeviceToHost, st));
   s->pref_ready = true;   // (whoever edits sel_cnt before S6 -- the sharded search's cut -- clears it)
@@ -1294,7 +1291,7 @@ static int run_maxsim(fp_index* ix, Scratch* s, const FpSearchShape& sh, int64_t
   if (mode != 2) {
     if (fpk_maxsim(D, s->qpad.as<uint16_t>(), sh, s->sel_pid.as<int32_t>(), s->sel_cnt.as<int32_t>(), R, s->exact.as<float>(),
                    s->ms_pref.as<int64_t>(), aux, st, pref_ready && s->pref_ready))
-      return fail(FP_EUNSUPPORTED, "dim/nbits");
+      return fp_fail(FP_EUNSUPPORTED, "dim/nbits");
     s->pref_ready = false;
     LAUNCHCHK("MaxSim");
   }
@@ -1372,8 +1369,8 @@ static int enqueue_batch(Pipe& P, const uint16_t* q_src, hipMemcpyKind q_kind, c
                                      s->fold_stats ? reinterpret_cast<int64_t*>(od + ol.stat_off) : nullptr,
                                      P.lazy ? reinterpret_cast<const int32_t*>(s->lz_state.as<uint32_t>() + 2 * B) : nullptr,
                                      P.total_folded ? s->spec_total.as<int64_t>() : nullptr))
-    return trc < 0 ? fail(FP_EUNSUPPORTED, "n_queries * max(n_full_scores / 4, 1) >= 2^31 in one sub-batch of the final ranking")
-                   : fail(FP_EHIP, "final ranking failed (hip error " + std::to_string(trc) + ")");
+    return trc < 0 ? fp_fail(FP_EUNSUPPORTED, "n_queries * max(n_full_scores / 4, 1) >= 2^31 in one sub-batch of the final ranking")
+                   : fp_fail(FP_EHIP, "final ranking failed (hip error " + std::to_string(trc) + ")");
   if (dev_io) {
     HIPCHK(hipMemcpyAsync(dev_pids, od, ol.nk * 8, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(dev_scores, od + ol.score_off, ol.nk * 4, hipMemcpyDeviceToDevice, st));
@@ -1525,7 +1522,7 @@ static int search_impl(fp_index* ix, const uint16_t* queries, int32_t nq, int32_
     return FP_OK;
   }
   Scratch* s = acquire(ix);
-  if (!s) return fail(FP_EHIP, "could not create a HIP stream");
+  if (!s) return fp_fail(FP_EHIP, "could not create a HIP stream");
   struct Rel {
     fp_index* ix; Scratch* s;
     ~Rel() {
@@ -1737,9 +1734,9 @@ extern "C" int fp_search_shared_subset(const fp_index* index, const uint16_t* qu
                                        const fp_search_params* params, const int64_t* subset_ids, int64_t n_subset, int64_t* out_pids,
                                        float* out_scores, int32_t* out_counts) {
   if (int rc = validate_search(index, n_queries, q_len, dim, params)) return rc;
-  if (n_subset < 0 || (n_subset > 0 && !subset_ids)) return fail(FP_EINVAL, "subset");
+  if (n_subset < 0 || (n_subset > 0 && !subset_ids)) return fp_fail(FP_EINVAL, "subset");
   if (n_queries > 0 && (!queries || !out_counts || (params->top_k > 0 && (!out_pids || !out_scores))))
-    return fail(FP_EINVAL, "null buffer");
+    return fp_fail(FP_EINVAL, "null buffer");
   return search_impl(const_cast<fp_index*>(index), queries, n_queries, q_len, params, subset_ids, nullptr, out_pids, out_scores, out_counts, nullptr,
                      false, n_subset);
 }
@@ -1749,7 +1746,7 @@ extern "C" int fp_search(const fp_index* index, const uint16_t* queries, int32_t
                          float* out_scores, int32_t* out_counts) {
   if (int rc = validate_search(index, n_queries, q_len, dim, params)) return rc;
   if (n_queries > 0 && (!queries || !out_counts || (params->top_k > 0 && (!out_pids || !out_scores))))
-    return fail(FP_EINVAL, "null buffer");
+    return fp_fail(FP_EINVAL, "null buffer");
   return search_impl(const_cast<fp_index*>(index), queries, n_queries, q_len, params, subset_ids, subset_offsets, out_pids, out_scores,
                      out_counts, nullptr);
 }
@@ -1763,7 +1760,7 @@ extern "C" int64_t fp_device_free_bytes(int device_id) { return mem_info(device_
 extern "C" int64_t fp_device_total_bytes(int device_id) { return mem_info(device_id, false); }
 
 extern "C" int fp_dev_alloc(int device_id, size_t bytes, void** out) {
-  if (!out) return fail(FP_EINVAL, "null argument");
+  if (!out) return fp_fail(FP_EINVAL, "null argument");
   *out = nullptr;
   HIPCHK(fp_set_device(device_id));
   HIPCHK(hipMalloc(out, bytes ? bytes : 1));
@@ -1775,13 +1772,13 @@ extern "C" int fp_dev_free(int device_id, void* p) {
   return FP_OK;
 }
 extern "C" int fp_dev_upload(int device_id, void* dst, const void* src, size_t bytes) {
-  if (bytes && (!dst || !src)) return fail(FP_EINVAL, "null argument");
+  if (bytes && (!dst || !src)) return fp_fail(FP_EINVAL, "null argument");
   HIPCHK(fp_set_device(device_id));
   HIPCHK(copy_sync(dst, src, bytes, hipMemcpyHostToDevice, util_stream(device_id)));
   return FP_OK;
 }
 extern "C" int fp_dev_download(int device_id, void* dst, const void* src, size_t bytes) {
-  if (bytes && (!dst || !src)) return fail(FP_EINVAL, "null argument");
+  if (bytes && (!dst || !src)) return fp_fail(FP_EINVAL, "null argument");
   HIPCHK(fp_set_device(device_id));
   HIPCHK(copy_sync(dst, src, bytes, hipMemcpyDeviceToHost, util_stream(device_id)));
   return FP_OK;
@@ -1791,7 +1788,7 @@ extern "C" int fp_search_device(const fp_index* index, const uint16_t* dev_queri
                                 const fp_search_params* params, int64_t* dev_out_pids, float* dev_out_scores, int32_t* dev_out_counts) {
   if (int rc = validate_search(index, n_queries, q_len, dim, params)) return rc;
   if (n_queries > 0 && (!dev_queries || !dev_out_counts || (params->top_k > 0 && (!dev_out_pids || !dev_out_scores))))
-    return fail(FP_EINVAL, "null argument");
+    return fp_fail(FP_EINVAL, "null argument");
   return search_impl(const_cast<fp_index*>(index), dev_queries, n_queries, q_len, params, nullptr, nullptr, dev_out_pids, dev_out_scores,
                      dev_out_counts, nullptr, true);
 }
@@ -1841,20 +1838,20 @@ extern "C" int fp_last_search_timings(const char** names, float* ms, int cap) {
 extern "C" int fp_maxsim_columns(const fp_index* cix, const uint16_t* query, int32_t Q, int32_t dim, const int64_t* pids, int64_t n,
                                  float* scores, uint16_t* col_max, float* unc, uint32_t* flags) {
   fp_index* ix = const_cast<fp_index*>(cix);
-  if (!ix || !query || Q < 1 || (n > 0 && (!pids || !scores))) return fail(FP_EINVAL, "bad argument");
-  if (dim != ix->d.dim) return fail(FP_EINVAL, "query dim does not match the index dim");
+  if (!ix || !query || Q < 1 || (n > 0 && (!pids || !scores))) return fp_fail(FP_EINVAL, "bad argument");
+  if (dim != ix->d.dim) return fp_fail(FP_EINVAL, "query dim does not match the index dim");
   if (n == 0) return FP_OK;
-  if (n > (1 << 24)) return fail(FP_EINVAL, "too many documents");
+  if (n > (1 << 24)) return fp_fail(FP_EINVAL, "too many documents");
   const FpIndexDev& D = ix->d;
   HIPCHK(fp_set_device(ix->device));
   std::vector<int32_t> loc((size_t)n);
   for (int64_t i = 0; i < n; ++i) {
     const int64_t d = pids[i] - D.pid_offset;
-    if (d < 0 || d >= D.N) return fail(FP_EINVAL, "document id out of range");
+    if (d < 0 || d >= D.N) return fp_fail(FP_EINVAL, "document id out of range");
     loc[(size_t)i] = (int32_t)d;
   }
   Scratch* s = acquire(ix);
-  if (!s) return fail(FP_EHIP, "could not create a HIP stream");
+  if (!s) return fp_fail(FP_EHIP, "could not create a HIP stream");
   struct Rel { fp_index* ix; Scratch* s; ~Rel() { release(ix, s); } } rel{ix, s};
   hipStream_t st = s->st;
   fp_search_params prm{0, 4, 1, 1};
@@ -1882,7 +1879,7 @@ extern "C" int fp_maxsim_columns(const fp_index* cix, const uint16_t* query, int
   FpMaxsimAux aux{fast ? s->ms_cm16.as<uint16_t>() : nullptr, s->ms_unc.as<float>(), fast ? s->ms_flags.as<uint32_t>() : nullptr, s->ms_uncm.as<float>()};
   if (fpk_maxsim(D, s->qpad.as<uint16_t>(), sh, s->sel_pid.as<int32_t>(), s->sel_cnt.as<int32_t>(), n, s->exact.as<float>(),
                  s->ms_pref.as<int64_t>(), aux, st))
-    return fail(FP_EUNSUPPORTED, "dim/nbits");
+    return fp_fail(FP_EUNSUPPORTED, "dim/nbits");
   HIPCHK(hipMemcpyAsync(scores, s->exact.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
   if (unc) HIPCHK(hipMemcpyAsync(unc, s->ms_unc.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
   // the caller's `flags` is [n, ceil(q_len / 32)] (fastplaid.h); the device rows are Qp / 32 words wide, which is MORE for
@@ -1915,12 +1912,12 @@ extern "C" int fp_maxsim_columns(const fp_index* cix, const uint16_t* query, int
 extern "C" int fp_reconstruct_embeddings(const fp_index* cix, const int64_t* doc_ids, int64_t n, float* out, int64_t cap_rows,
                                          int64_t* out_lengths) {
   fp_index* ix = const_cast<fp_index*>(cix);
-  if (!ix || (n > 0 && (!doc_ids || !out_lengths))) return fail(FP_EINVAL, "null argument");
+  if (!ix || (n > 0 && (!doc_ids || !out_lengths))) return fp_fail(FP_EINVAL, "null argument");
   HIPCHK(fp_set_device(ix->device));
   std::vector<int64_t> tok;
   for (int64_t i = 0; i < n; ++i) {
     int64_t d = doc_ids[i] - ix->d.pid_offset;
-    if (d < 0 || d >= ix->d.N) return fail(FP_EINVAL, "document id out of range");
+    if (d < 0 || d >= ix->d.N) return fp_fail(FP_EINVAL, "document id out of range");
     const int64_t o = ix->h_doc_off[d], l = ix->h_doc_off[d + 1] - o;
     out_lengths[i] = l;
     const size_t base = tok.size();
@@ -1934,16 +1931,16 @@ extern "C" int fp_reconstruct_embeddings(const fp_index* cix, const int64_t* doc
     }
   }
   const int64_t rows = (int64_t)tok.size();
-  if (rows > cap_rows) return fail(FP_EINVAL, "output capacity too small");
+  if (rows > cap_rows) return fp_fail(FP_EINVAL, "output capacity too small");
   if (rows == 0) return FP_OK;
   Scratch* s = acquire(ix);
-  if (!s) return fail(FP_EHIP, "could not create a HIP stream");
+  if (!s) return fp_fail(FP_EHIP, "could not create a HIP stream");
   struct Rel { fp_index* ix; Scratch* s; ~Rel() { release(ix, s); } } rel{ix, s};
   HIPCHK(s->tok_idx.ensure((size_t)rows * 8));
   HIPCHK(s->recon.ensure((size_t)rows * ix->d.dim * 4));
   HIPCHK(hipMemcpyAsync(s->tok_idx.p, tok.data(), (size_t)rows * 8, hipMemcpyHostToDevice, s->st));
   if (fpk_tok_tiled()) fpk_reconstruct_units(ix->d, s->tok_idx.as<int64_t>(), rows, s->recon.as<float>(), s->st);
-  else if (ix->d.dim > 512) return fail(FP_EUNSUPPORTED, "FP_TEST=tok_tiled=0: k_reconstruct serves dim <= 512 only");
+  else if (ix->d.dim > 512) return fp_fail(FP_EUNSUPPORTED, "FP_TEST=tok_tiled=0: k_reconstruct serves dim <= 512 only");
   else fpk_reconstruct(ix->d, s->tok_idx.as<int64_t>(), rows, s->recon.as<float>(), s->st);
   HIPCHK(hipMemcpyAsync(out, s->recon.p, (size_t)rows * ix->d.dim * 4, hipMemcpyDeviceToHost, s->st));
   HIPCHK(hipStreamSynchronize(s->st));
@@ -1956,20 +1953,20 @@ extern "C" int fp_reconstruct_embeddings(const fp_index* cix, const int64_t* doc
 extern "C" int fp_token_scores(const fp_index* cix, const uint16_t* queries, int32_t nq, int32_t Q, int32_t dim, const int64_t* pids,
                                const int32_t* counts, int64_t stride, int64_t* out_offsets, uint16_t* out, int64_t out_capacity) {
   fp_index* ix = const_cast<fp_index*>(cix);
-  if (!ix || nq < 0 || (nq > 0 && (!queries || !pids || !counts)) || !out_offsets) return fail(FP_EINVAL, "null argument");
-  if (dim != ix->d.dim) return fail(FP_EINVAL, "query dim does not match the index");
-  if (Q < 1) return fail(FP_EINVAL, "need at least one query token");
+  if (!ix || nq < 0 || (nq > 0 && (!queries || !pids || !counts)) || !out_offsets) return fp_fail(FP_EINVAL, "null argument");
+  if (dim != ix->d.dim) return fp_fail(FP_EINVAL, "query dim does not match the index");
+  if (Q < 1) return fp_fail(FP_EINVAL, "need at least one query token");
   HIPCHK(fp_set_device(ix->device));
   std::vector<int32_t> hq, hp, tiles;   // tiles: {hit, first stored token, first query row} per 64 x 64 tile (k_token_scores_tile)
   const bool tiled = fpk_tok_tiled();
   int64_t off = 0, h = 0;
   out_offsets[0] = 0;
   for (int32_t b = 0; b < nq; ++b) {
-    if (counts[b] < 0 || counts[b] > stride) return fail(FP_EINVAL, "bad hit count");
+    if (counts[b] < 0 || counts[b] > stride) return fp_fail(FP_EINVAL, "bad hit count");
     for (int32_t i = 0; i < counts[b]; ++i) {
       const int64_t d = pids[(int64_t)b * stride + i] - ix->d.pid_offset;
-      if (d < 0 || d >= ix->d.N) return fail(FP_EINVAL, "document id out of range");
-      if (h >= 0x7FFFFFFFll) return fail(FP_EUNSUPPORTED, "more than 2^31 - 1 hits in one call");
+      if (d < 0 || d >= ix->d.N) return fp_fail(FP_EINVAL, "document id out of range");
+      if (h >= 0x7FFFFFFFll) return fp_fail(FP_EUNSUPPORTED, "more than 2^31 - 1 hits in one call");
       const int64_t len = ix->h_doc_off[d + 1] - ix->h_doc_off[d];
       if (out && tiled)
         for (int64_t s0 = 0; s0 < len; s0 += 64)
@@ -1981,9 +1978,9 @@ extern "C" int fp_token_scores(const fp_index* cix, const uint16_t* queries, int
     }
   }
   if (!out || h == 0 || off == 0) return FP_OK;   // sizing call, or nothing to compute
-  if (off > out_capacity) return fail(FP_EINVAL, "output capacity too small");
+  if (off > out_capacity) return fp_fail(FP_EINVAL, "output capacity too small");
   Scratch* s = acquire(ix);
-  if (!s) return fail(FP_EHIP, "could not create a HIP stream");
+  if (!s) return fp_fail(FP_EHIP, "could not create a HIP stream");
   struct Rel { fp_index* ix; Scratch* s; ~Rel() { release(ix, s); } } rel{ix, s};
   const size_t qbytes = (size_t)nq * Q * dim * 2;
   HIPCHK(s->qin.ensure(qbytes));
@@ -2002,465 +1999,10 @@ extern "C" int fp_token_scores(const fp_index* cix, const uint16_t* queries, int
     fpk_token_scores_tile(ix->d, s->qin.as<uint16_t>(), Q, d_hq, d_hp, s->tmpp.as<int64_t>(), d_tiles, (int64_t)(tiles.size() / 3),
                           s->recon.as<uint16_t>(), s->st);
   } else if (fpk_token_scores(ix->d, s->qin.as<uint16_t>(), Q, d_hq, d_hp, h, s->tmpp.as<int64_t>(), s->recon.as<uint16_t>(), s->st)) {
-    return fail(FP_EUNSUPPORTED, "q_len * dim too large for the token-score kernel");
+    return fp_fail(FP_EUNSUPPORTED, "q_len * dim too large for the token-score kernel");
   }
   HIPCHK(hipMemcpyAsync(out, s->recon.p, (size_t)off * 2, hipMemcpyDeviceToHost, s->st));
   HIPCHK(hipStreamSynchronize(s->st));
-  return FP_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// index creation, device part (create.rs:148-184, :404-428)
-// ------------------------------------------------------------------------------------------
-// dims of the nearest-centroid assignment (fp_index_ops.hip): [1, 256], and every multiple of 8 up to 1024
-static bool assign_dim_accepted(int32_t dim) { return dim >= 1 && (dim <= 256 || (dim <= 1024 && dim % 8 == 0)); }
-
-enum { CP_CHUNKS, CP_NARROWED, CP_FALLBACK, CP_US_ASSIGN, CP_US_PACK, CP_CAND_SUM, CP_CAND_MAX, CP_N };
-static thread_local int64_t g_cp[CP_N];
-static thread_local int g_cp_have = 0;   // 1: the figures are those of a call that succeeded
-extern "C" int fp_compress_last_counts(int64_t* out, int cap) {
-  if (!out || cap < 0) return 0;
-  for (int i = 0; i < std::min(cap, (int)CP_N); ++i) out[i] = g_cp[i];
-  return g_cp_have;
-}
-
-extern "C" int fp_compress(int device_id, const uint16_t* centroids, int64_t C, int32_t dim, int32_t nbits, const uint16_t* cutoffs,
-                           const uint16_t* emb, int64_t T, int64_t* out_codes, uint8_t* out_res) {
-  g_cp_have = 0;
-  for (int64_t& v : g_cp) v = 0;
-  if (!centroids || !cutoffs || C < 1 || T < 0 || (T > 0 && (!emb || !out_codes || !out_res))) return fail(FP_EINVAL, "bad argument");
-  if (!(nbits == 1 || nbits == 2 || nbits == 4 || nbits == 8)) return fail(FP_EINVAL, "nbits must divide 8 (1, 2, 4 or 8)");
-  if (!assign_dim_accepted(dim) || (dim * nbits) % 8 != 0)
-    return fail(FP_EUNSUPPORTED, "fp_compress: dim must be in [1, 256] or a multiple of 8 up to 1024, with dim * nbits a multiple of 8");
-  if (C >= 0x7FFFFFFFll) return fail(FP_EUNSUPPORTED, "too many centroids");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(FP_EHIP, "no HIP device available (this library has no CPU path)");
-  if (device_id < 0 || device_id >= ndev) return fail(FP_EINVAL, "device index out of range");
-  HIPCHK(fp_set_device(device_id));
-  int64_t cp[CP_N] = {0, 0, 0, 0, 0, 0, 0};
-  if (T == 0) {
-    for (int i = 0; i < CP_N; ++i) g_cp[i] = cp[i];
-    g_cp_have = 1;
-    return FP_OK;
-  }
-  const int pr = dim * nbits / 8;
-  const int64_t CHUNK = 1ll << 20;   // tokens per pass
-  const int64_t cap = std::min<int64_t>(T, CHUNK);
-  void *d_cent = nullptr, *d_cut = nullptr, *d_emb = nullptr, *d_c32 = nullptr, *d_c64 = nullptr, *d_out = nullptr, *d_work = nullptr;
-  hipStream_t st = nullptr;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  int rc = FP_OK;
-  float cmaxabs = 0.f;   // bounds the MFMA summation error in the assignment (fp16 -> float by hand: no device needed)
-  for (int64_t i = 0; i < C * dim; ++i) {
-    const uint16_t hbits = centroids[i] & 0x7FFF;
-    const int ex = hbits >> 10, ma = hbits & 0x3FF;
-    const float v = ex == 0 ? std::ldexp((float)ma, -24) : (ex == 31 ? INFINITY : std::ldexp((float)(ma | 0x400), ex - 25));
-    if (v > cmaxabs) cmaxabs = v;
-  }
-  auto cleanup = [&]() {
-    for (void* p : {d_cent, d_cut, d_emb, d_c32, d_c64, d_out, d_work})
-      if (p) (void)hipFree(p);
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-    if (st) (void)hipStreamDestroy(st);
-  };
-#define CCHK(x)                                                                                   \
-  do {                                                                                            \
-    hipError_t e_ = (x);                                                                          \
-    if (e_ != hipSuccess) {                                                                       \
-      cleanup();                                                                                  \
-      return fail(FP_EHIP, std::string("HIP error in fp_compress: ") + hipGetErrorString(e_));    \
-    }                                                                                             \
-  } while (0)
-  CCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  for (hipEvent_t& e : ev) CCHK(hipEventCreate(&e));
-  CCHK(hipMalloc(&d_cent, (size_t)C * dim * 2));
-  CCHK(hipMalloc(&d_cut, 1024));   // up to 255 cutoffs (nbits = 8)
-  CCHK(hipMalloc(&d_emb, (size_t)cap * dim * 2));
-  CCHK(hipMalloc(&d_c32, (size_t)cap * 4));
-  CCHK(hipMalloc(&d_c64, (size_t)cap * 8));
-  CCHK(hipMalloc(&d_out, (size_t)cap * pr));
-  CCHK(hipMalloc(&d_work, fpk_compress_work_bytes(cap)));
-  CCHK(hipMemcpyAsync(d_cent, centroids, (size_t)C * dim * 2, hipMemcpyHostToDevice, st));
-  CCHK(hipMemcpyAsync(d_cut, cutoffs, (size_t)((1 << nbits) - 1) * 2, hipMemcpyHostToDevice, st));
-  for (int64_t t0 = 0; t0 < T && rc == FP_OK; t0 += CHUNK) {
-    const int64_t n = std::min<int64_t>(CHUNK, T - t0);
-    CCHK(hipMemcpyAsync(d_emb, emb + t0 * dim, (size_t)n * dim * 2, hipMemcpyHostToDevice, st));
-    int64_t how[4] = {0, 0, 0, 0};
-    if (fpk_compress(static_cast<const uint16_t*>(d_emb), n, static_cast<const uint16_t*>(d_cent), C, dim, nbits,
-                     static_cast<const uint16_t*>(d_cut), cmaxabs, static_cast<int32_t*>(d_c32), static_cast<int64_t*>(d_c64),
-                     static_cast<uint8_t*>(d_out), d_work, st, how, ev)) {
-      cleanup();
-      return fail(FP_EUNSUPPORTED, "dim");
-    }
-    CCHK(hipMemcpyAsync(out_codes + t0, d_c64, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    CCHK(hipMemcpyAsync(out_res + t0 * pr, d_out, (size_t)n * pr, hipMemcpyDeviceToHost, st));
-    CCHK(hipStreamSynchronize(st));
-    ++cp[CP_CHUNKS];
-    cp[CP_NARROWED] += how[0];
-    cp[CP_FALLBACK] += how[1];
-    cp[CP_CAND_SUM] += how[2];
-    cp[CP_CAND_MAX] = std::max(cp[CP_CAND_MAX], how[3]);
-    for (int s = 0; s < 2; ++s) {
-      float ms = 0.f;
-      CCHK(hipEventElapsedTime(&ms, ev[s], ev[s + 1]));
-      cp[CP_US_ASSIGN + s] += (int64_t)(ms * 1000.f + 0.5f);
-    }
-  }
-#undef CCHK
-  cleanup();
-  for (int i = 0; i < CP_N; ++i) g_cp[i] = cp[i];
-  g_cp_have = 1;
-  return rc;
-}
-
-extern "C" int fp_assign_l2(int device_id, const uint16_t* centroids, const float* half_sqnorm, int64_t C, int32_t dim, const uint16_t* emb,
-                            int64_t T, int64_t* out_labels) {
-  if (!centroids || !half_sqnorm || C < 1 || T < 0 || (T > 0 && (!emb || !out_labels))) return fail(FP_EINVAL, "bad argument");
-  if (!assign_dim_accepted(dim)) return fail(FP_EUNSUPPORTED, "fp_assign_l2: dim must be in [1, 256] or a multiple of 8 up to 1024");
-  if (C >= 0x7FFFFFFFll) return fail(FP_EUNSUPPORTED, "too many centroids");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(FP_EHIP, "no HIP device available (this library has no CPU path)");
-  if (device_id < 0 || device_id >= ndev) return fail(FP_EINVAL, "device index out of range");
-  HIPCHK(fp_set_device(device_id));
-  if (T == 0) return FP_OK;
-  const int64_t CHUNK = 1ll << 20;
-  const int64_t cap = std::min<int64_t>(T, CHUNK);
-  void *d_cent = nullptr, *d_hn = nullptr, *d_emb = nullptr, *d_c32 = nullptr, *d_c64 = nullptr;
-  hipStream_t st = nullptr;
-  auto cleanup = [&]() {
-    for (void* p : {d_cent, d_hn, d_emb, d_c32, d_c64})
-      if (p) (void)hipFree(p);
-    if (st) (void)hipStreamDestroy(st);
-  };
-#define ACHK(x)                                                                                   \
-  do {                                                                                            \
-    hipError_t e_ = (x);                                                                          \
-    if (e_ != hipSuccess) {                                                                       \
-      cleanup();                                                                                  \
-      return fail(FP_EHIP, std::string("HIP error in fp_assign_l2: ") + hipGetErrorString(e_));   \
-    }                                                                                             \
-  } while (0)
-  ACHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  ACHK(hipMalloc(&d_cent, (size_t)C * dim * 2));
-  ACHK(hipMalloc(&d_hn, (size_t)C * 4));
-  ACHK(hipMalloc(&d_emb, (size_t)cap * dim * 2));
-  ACHK(hipMalloc(&d_c32, (size_t)cap * 4));
-  ACHK(hipMalloc(&d_c64, (size_t)cap * 8));
-  ACHK(hipMemcpyAsync(d_cent, centroids, (size_t)C * dim * 2, hipMemcpyHostToDevice, st));
-  ACHK(hipMemcpyAsync(d_hn, half_sqnorm, (size_t)C * 4, hipMemcpyHostToDevice, st));
-  for (int64_t t0 = 0; t0 < T; t0 += CHUNK) {
-    const int64_t n = std::min<int64_t>(CHUNK, T - t0);
-    ACHK(hipMemcpyAsync(d_emb, emb + t0 * dim, (size_t)n * dim * 2, hipMemcpyHostToDevice, st));
-    if (fpk_assign_l2(static_cast<const uint16_t*>(d_emb), n, static_cast<const uint16_t*>(d_cent), static_cast<const float*>(d_hn), C, dim,
-                      static_cast<int32_t*>(d_c32), static_cast<int64_t*>(d_c64), st)) {
-      cleanup();
-      return fail(FP_EUNSUPPORTED, "dim");
-    }
-    ACHK(hipMemcpyAsync(out_labels + t0, d_c64, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    ACHK(hipStreamSynchronize(st));
-  }
-#undef ACHK
-  cleanup();
-  return FP_OK;
-}
-
-// k-means trainer (fastplaid.h fp_kmeans): the sample goes up once, every Lloyd iteration runs on the device; per iteration only the
-// chunks' overflow counters of the MFMA narrowing come back (a chunk with a non-zero counter is assigned again by the exact kernel).
-enum { KM_UPLOAD, KM_ASSIGN, KM_INDEX, KM_SUM, KM_FINALISE, KM_NARROWED, KM_FALLBACK, KM_N };   // five times, two chunk counts
-static thread_local float g_km_ms[KM_N];
-static thread_local int g_km_have = 0;   // iterations the figures of the last call cover (0: none)
-extern "C" int fp_kmeans_last_timings(float* ms, int cap) {
-  for (int i = 0; i < std::min(cap, (int)KM_N); ++i) ms[i] = g_km_ms[i];
-  return g_km_have;
-}
-
-extern "C" int fp_kmeans(int device_id, const uint16_t* data, int64_t n, int32_t dim, int64_t k, int32_t niter, const int64_t* init_rows,
-                         uint64_t seed, float* out_centroids, int64_t* out_counts) {
-  g_km_have = 0;
-  if (!data || !init_rows || !out_centroids || n < 1 || k < 1 || niter < 0) return fail(FP_EINVAL, "bad argument");
-  if (!assign_dim_accepted(dim)) return fail(FP_EUNSUPPORTED, "fp_kmeans: dim must be in [1, 256] or a multiple of 8 up to 1024");
-  if (k > n) return fail(FP_EINVAL, "fp_kmeans: fewer training points (" + std::to_string(n) + ") than centroids (" + std::to_string(k) + ")");
-  if (n >= 0x7FFFFFFFll) return fail(FP_EUNSUPPORTED, "fp_kmeans: more than 2^31-2 training points");
-  for (int64_t c = 0; c < k; ++c)
-    if (init_rows[c] < 0 || init_rows[c] >= n) return fail(FP_EINVAL, "fp_kmeans: init_rows[" + std::to_string(c) + "] outside [0, n)");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(FP_EHIP, "no HIP device available (this library has no CPU path)");
-  if (device_id < 0 || device_id >= ndev) return fail(FP_EINVAL, "device index out of range");
-  HIPCHK(fp_set_device(device_id));
-  const int64_t chunk_opt = (int64_t)fp_test_opt("kmeans_chunk", 0);   // tests: a chunk boundary inside a few thousand points
-  const int64_t CHUNK = std::min<int64_t>(n, chunk_opt > 0 ? chunk_opt : (1ll << 20));
-  const int64_t nchunk = (n + CHUNK - 1) / CHUNK;
-  const bool timed = niter > 0 && niter <= 64;
-  void *d_data = nullptr, *d_init = nullptr, *d_lab = nullptr, *d_mem = nullptr, *d_c32 = nullptr, *d_c16 = nullptr, *d_hn = nullptr,
-       *d_sums = nullptr, *d_cnt = nullptr, *d_cur = nullptr, *d_cnt64 = nullptr, *d_work = nullptr, *d_over = nullptr,
-       *d_stat = nullptr;
-  hipStream_t st = nullptr;
-  std::vector<hipEvent_t> ev;
-  auto cleanup = [&]() {
-    for (void* p : {d_data, d_init, d_lab, d_mem, d_c32, d_c16, d_hn, d_sums, d_cnt, d_cur, d_cnt64, d_work, d_over, d_stat})
-      if (p) (void)hipFree(p);
-    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    if (st) (void)hipStreamDestroy(st);
-  };
-#define KCHK(x)                                                                                \
-  do {                                                                                         \
-    hipError_t e_ = (x);                                                                       \
-    if (e_ != hipSuccess) {                                                                    \
-      cleanup();                                                                               \
-      (void)hipGetLastError();                                                                 \
-      return fail(e_ == hipErrorOutOfMemory ? FP_ENOMEM : FP_EHIP, std::string("HIP error in fp_kmeans: ") + hipGetErrorString(e_) + " at " #x); \
-    }                                                                                          \
-  } while (0)
-  const size_t kd = (size_t)k * dim;
-  struct { void** p; size_t bytes; } bufs[] = {
-      {&d_data, (size_t)n * dim * 2}, {&d_init, (size_t)k * 8}, {&d_lab, (size_t)n * 4}, {&d_mem, (size_t)n * 4}, {&d_c32, kd * 4},
-      {&d_c16, kd * 2}, {&d_hn, (size_t)k * 4}, {&d_sums, kd * 8}, {&d_cnt, (size_t)k * 4},
-      {&d_cur, (size_t)k * 4}, {&d_cnt64, (size_t)k * 8}, {&d_work, fpk_compress_work_bytes(CHUNK)}, {&d_over, (size_t)nchunk * 4},
-      {&d_stat, 64}};
-  size_t need = 0, mfree = 0, mtotal = 0;
-  for (auto& b : bufs) need += b.bytes + 256;
-  KCHK(hipMemGetInfo(&mfree, &mtotal));
-  if (need > mfree)
-    return fail(FP_ENOMEM, "fp_kmeans: the sample and its work buffers need " + std::to_string(need) + " bytes of device memory, " +
-                               std::to_string(mfree) + " are free");
-  KCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  for (auto& b : bufs) KCHK(hipMalloc(b.p, b.bytes));
-  if (timed) {
-    ev.resize(2 + 5 * (size_t)niter, nullptr);
-    for (hipEvent_t& e : ev) KCHK(hipEventCreate(&e));
-  }
-  const uint16_t* data_d = static_cast<const uint16_t*>(d_data);
-  uint32_t* stat = static_cast<uint32_t*>(d_stat);   // [0..1] {max|cent16|, max hn} of the iteration, [4] max |x| bits of the data
-  int32_t* labels = static_cast<int32_t*>(d_lab);
-  if (timed) KCHK(hipEventRecord(ev[0], st));
-  KCHK(hipMemsetAsync(d_stat, 0, 64, st));
-  KCHK(hipMemcpyAsync(d_data, data, (size_t)n * dim * 2, hipMemcpyHostToDevice, st));
-  KCHK(hipMemcpyAsync(d_init, init_rows, (size_t)k * 8, hipMemcpyHostToDevice, st));
-  fpk_km_scan_data(data_d, n * dim, stat + 4, st);
-  uint32_t h_xmax = 0;
-  KCHK(hipMemcpyAsync(&h_xmax, stat + 4, 4, hipMemcpyDeviceToHost, st));
-  if (timed) KCHK(hipEventRecord(ev[1], st));
-  KCHK(hipStreamSynchronize(st));
-  KCHK(hipGetLastError());
-  if (h_xmax >= 0x7C00u) {
-    cleanup();
-    return fail(FP_EINVAL, "fp_kmeans: the data holds a value that is not finite");
-  }
-  // exact sums in int64 units of 2^-24: refuse what could leave 2^62
-  if ((unsigned __int128)n * (unsigned __int128)fp_f16_fixed((uint16_t)h_xmax) >= ((unsigned __int128)1 << 62)) {
-    cleanup();
-    return fail(FP_EUNSUPPORTED, "fp_kmeans: n * max|x| * 2^24 >= 2^62 (the exact fixed-point sums could overflow)");
-  }
-  fpk_km_finalise(data_d, n, dim, k, static_cast<const int64_t*>(d_init), nullptr, nullptr, seed, 0, static_cast<float*>(d_c32),
-                  static_cast<uint16_t*>(d_c16), static_cast<float*>(d_hn), stat, st);
-  std::vector<int32_t> h_over((size_t)nchunk, 0);
-  int64_t n_narrowed = 0, n_fallback = 0;   // chunk assignments through the MFMA narrowing / of those, sent on to the exact kernel
-  for (int it = 0; it < niter; ++it) {
-    hipEvent_t* e = timed ? &ev[2 + 5 * (size_t)it] : nullptr;
-    if (e) KCHK(hipEventRecord(e[0], st));
-    KCHK(hipMemsetAsync(d_over, 0, (size_t)nchunk * 4, st));
-    bool narrowed = false;
-    for (int64_t ci = 0; ci < nchunk; ++ci) {
-      const int64_t t0 = ci * CHUNK, nn = std::min<int64_t>(CHUNK, n - t0);
-      const int rc = fpk_assign_l2_narrow(data_d + t0 * dim, nn, static_cast<const uint16_t*>(d_c16), static_cast<const float*>(d_hn), stat, k, dim,
-                                          labels + t0, d_work, static_cast<int32_t*>(d_over) + ci, st);
-      if (rc < 0) {
-        cleanup();
-        return fail(FP_EUNSUPPORTED, "fp_kmeans: assignment chunk (" + std::to_string(rc) + ")");
-      }
-      narrowed |= rc == 1;
-      n_narrowed += rc == 1;
-    }
-    if (narrowed) {   // the fallback flags: the only thing that returns to the host between iterations
-      KCHK(hipMemcpyAsync(h_over.data(), d_over, (size_t)nchunk * 4, hipMemcpyDeviceToHost, st));
-      KCHK(hipStreamSynchronize(st));
-      for (int64_t ci = 0; ci < nchunk; ++ci) {
-        if (h_over[(size_t)ci] == 0) continue;   // else: a point met more than ASSIGN_CAP near-tied centroids
-        ++n_fallback;
-        const int64_t t0 = ci * CHUNK, nn = std::min<int64_t>(CHUNK, n - t0);
-        if (fpk_assign_l2_exact(data_d + t0 * dim, nn, static_cast<const uint16_t*>(d_c16), static_cast<const float*>(d_hn), k, dim, labels + t0, st)) {
-          cleanup();
-          return fail(FP_EUNSUPPORTED, "fp_kmeans: assignment chunk");
-        }
-      }
-    }
-    if (e) KCHK(hipEventRecord(e[1], st));
-    fpk_km_index(labels, n, k, static_cast<int32_t*>(d_cnt), static_cast<int32_t*>(d_cur), static_cast<int32_t*>(d_mem), st);
-    if (e) KCHK(hipEventRecord(e[2], st));
-    fpk_km_sum(data_d, n, dim, k, labels, static_cast<const int32_t*>(d_mem), static_cast<int64_t*>(d_sums), st);
-    if (e) KCHK(hipEventRecord(e[3], st));
-    fpk_km_finalise(data_d, n, dim, k, nullptr, static_cast<const int64_t*>(d_sums), static_cast<const int32_t*>(d_cnt), seed, it,
-                    static_cast<float*>(d_c32), static_cast<uint16_t*>(d_c16), static_cast<float*>(d_hn), stat, st);
-    if (e) KCHK(hipEventRecord(e[4], st));
-    KCHK(hipGetLastError());
-  }
-  KCHK(hipMemcpyAsync(out_centroids, d_c32, kd * 4, hipMemcpyDeviceToHost, st));
-  if (out_counts) {
-    if (niter > 0) {
-      fpk_km_widen_counts(static_cast<const int32_t*>(d_cnt), static_cast<int64_t*>(d_cnt64), k, st);
-      KCHK(hipMemcpyAsync(out_counts, d_cnt64, (size_t)k * 8, hipMemcpyDeviceToHost, st));
-    } else {
-      memset(out_counts, 0, (size_t)k * 8);
-    }
-  }
-  KCHK(hipStreamSynchronize(st));
-  KCHK(hipGetLastError());
-  if (timed) {
-    float ms[KM_N] = {0.f, 0.f, 0.f, 0.f, 0.f, (float)n_narrowed, (float)n_fallback}, x = 0.f;
-    KCHK(hipEventElapsedTime(&ms[KM_UPLOAD], ev[0], ev[1]));
-    for (int it = 0; it < niter; ++it)
-      for (int s = 0; s < 4; ++s) {
-        KCHK(hipEventElapsedTime(&x, ev[2 + 5 * (size_t)it + s], ev[3 + 5 * (size_t)it + s]));
-        ms[KM_ASSIGN + s] += x;
-      }
-    for (int i = 0; i < KM_N; ++i) g_km_ms[i] = ms[i];
-    g_km_have = niter;
-  }
-#undef KCHK
-  cleanup();
-  return FP_OK;
-}
-
-// Outliers of a centroid table (fastplaid.h fp_centroid_outliers): the centroids go up once, the embeddings in chunks; per chunk
-// the overflow counter of the MFMA narrowing, the data check and the outlier count come back, then that many rows.
-enum { CO_CHUNKS, CO_NARROWED, CO_FALLBACK, CO_US_UPLOAD, CO_US_ASSIGN, CO_US_OUTLIER, CO_US_DOWNLOAD, CO_N };
-static thread_local int64_t g_co[CO_N];
-static thread_local int g_co_have = 0;   // 1: the figures are those of a call that succeeded
-extern "C" int fp_centroid_outliers_last_counts(int64_t* out, int cap) {
-  for (int i = 0; i < std::min(cap, (int)CO_N); ++i) out[i] = g_co[i];
-  return g_co_have;
-}
-
-extern "C" int fp_centroid_outliers(int device_id, const uint16_t* centroids, int64_t C, int32_t dim, const uint16_t* emb, int64_t T,
-                                    float threshold_sq, int64_t* out_rows, int64_t* out_count, float* out_sqdist, int64_t* out_nearest) {
-  g_co_have = 0;
-  if (!out_count) return fail(FP_EINVAL, "bad argument");
-  *out_count = 0;
-  if (!centroids || C < 1 || T < 0 || (T > 0 && (!emb || !out_rows))) return fail(FP_EINVAL, "bad argument");
-  if (!(threshold_sq >= 0.f)) return fail(FP_EINVAL, "fp_centroid_outliers: threshold_sq must be a number >= 0");
-  if (!assign_dim_accepted(dim))
-    return fail(FP_EUNSUPPORTED, "fp_centroid_outliers: dim must be in [1, 256] or a multiple of 8 up to 1024");
-  if (C >= 0x7FFFFFFFll) return fail(FP_EUNSUPPORTED, "too many centroids");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(FP_EHIP, "no HIP device available (this library has no CPU path)");
-  if (device_id < 0 || device_id >= ndev) return fail(FP_EINVAL, "device index out of range");
-  HIPCHK(fp_set_device(device_id));
-  int64_t co[CO_N] = {0, 0, 0, 0, 0, 0, 0};
-  if (T == 0) {
-    for (int i = 0; i < CO_N; ++i) g_co[i] = co[i];
-    g_co_have = 1;
-    return FP_OK;
-  }
-  const int64_t chunk_opt = (int64_t)fp_test_opt("outlier_chunk", 0);   // tests: chunk boundaries inside a few thousand tokens
-  const int64_t CHUNK = std::min<int64_t>(T, chunk_opt > 0 ? chunk_opt : (1ll << 20));
-  const size_t ntile = fpk_outliers_tiles(CHUNK);
-  void *d_cent = nullptr, *d_hn = nullptr, *d_emb = nullptr, *d_lab = nullptr, *d_sq = nullptr, *d_near = nullptr, *d_flag = nullptr,
-       *d_tcnt = nullptr, *d_toff = nullptr, *d_rows = nullptr, *d_work = nullptr, *d_stat = nullptr;
-  hipStream_t st = nullptr;
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  auto cleanup = [&]() {
-    for (void* p : {d_cent, d_hn, d_emb, d_lab, d_sq, d_near, d_flag, d_tcnt, d_toff, d_rows, d_work, d_stat})
-      if (p) (void)hipFree(p);
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-    if (st) (void)hipStreamDestroy(st);
-  };
-#define OCHK(x)                                                                                \
-  do {                                                                                         \
-    hipError_t e_ = (x);                                                                       \
-    if (e_ != hipSuccess) {                                                                    \
-      cleanup();                                                                               \
-      (void)hipGetLastError();                                                                 \
-      return fail(e_ == hipErrorOutOfMemory ? FP_ENOMEM : FP_EHIP,                             \
-                  std::string("HIP error in fp_centroid_outliers: ") + hipGetErrorString(e_) + " at " #x); \
-    }                                                                                          \
-  } while (0)
-  struct { void** p; size_t bytes; } bufs[] = {
-      {&d_cent, (size_t)C * dim * 2}, {&d_hn, (size_t)C * 4}, {&d_emb, (size_t)CHUNK * dim * 2}, {&d_lab, (size_t)CHUNK * 4},
-      {&d_sq, (size_t)CHUNK * 4}, {&d_near, out_nearest ? (size_t)CHUNK * 8 : 0}, {&d_flag, (size_t)CHUNK}, {&d_tcnt, ntile * 4},
-      {&d_toff, ntile * 4}, {&d_rows, (size_t)CHUNK * 8}, {&d_work, fpk_compress_work_bytes(CHUNK)}, {&d_stat, 64}};
-  OCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  for (auto& b : bufs)
-    if (b.bytes) OCHK(hipMalloc(b.p, b.bytes));
-  for (hipEvent_t& e : ev) OCHK(hipEventCreate(&e));
-  // stat: [0..1] {max|cent|, max hn} (k_assign_thr_l2's input), [4] max |x| bits of the centroids, then of the embeddings so far,
-  // [8] the chunk's overflow counter, [9] its outlier count
-  uint32_t* stat = static_cast<uint32_t*>(d_stat);
-  const uint16_t* cent_d = static_cast<const uint16_t*>(d_cent);
-  const uint16_t* emb_d = static_cast<const uint16_t*>(d_emb);
-  const float* hn_d = static_cast<const float*>(d_hn);
-  int32_t* labels = static_cast<int32_t*>(d_lab);
-  OCHK(hipMemsetAsync(d_stat, 0, 64, st));
-  OCHK(hipMemcpyAsync(d_cent, centroids, (size_t)C * dim * 2, hipMemcpyHostToDevice, st));
-  fpk_km_scan_data(cent_d, C * dim, stat + 4, st);
-  fpk_out_prepare(cent_d, C, dim, static_cast<float*>(d_hn), stat, st);
-  uint32_t h_max = 0;
-  OCHK(hipMemcpyAsync(&h_max, stat + 4, 4, hipMemcpyDeviceToHost, st));
-  OCHK(hipStreamSynchronize(st));
-  OCHK(hipGetLastError());
-  if (h_max >= 0x7C00u) {
-    cleanup();
-    return fail(FP_EINVAL, "fp_centroid_outliers: the centroids hold a value that is not finite");
-  }
-  int64_t total = 0;
-  for (int64_t t0 = 0; t0 < T; t0 += CHUNK) {
-    const int64_t n = std::min<int64_t>(CHUNK, T - t0);
-    OCHK(hipEventRecord(ev[0], st));
-    OCHK(hipMemcpyAsync(d_emb, emb + t0 * dim, (size_t)n * dim * 2, hipMemcpyHostToDevice, st));
-    fpk_km_scan_data(emb_d, n * dim, stat + 4, st);
-    OCHK(hipEventRecord(ev[1], st));
-    const int rc = fpk_assign_l2_narrow(emb_d, n, cent_d, hn_d, stat, C, dim, labels, d_work, reinterpret_cast<int32_t*>(stat + 8), st);
-    if (rc < 0) {
-      cleanup();
-      return fail(FP_EUNSUPPORTED, "fp_centroid_outliers: assignment chunk (" + std::to_string(rc) + ")");
-    }
-    uint32_t h_chk[5] = {0, 0, 0, 0, 0};   // [0] max |x| bits, [4] overflow counter (zero when the chunk did not take the narrowing)
-    OCHK(hipMemcpyAsync(h_chk, stat + 4, sizeof(h_chk), hipMemcpyDeviceToHost, st));
-    OCHK(hipStreamSynchronize(st));
-    if (h_chk[0] >= 0x7C00u) {
-      cleanup();
-      return fail(FP_EINVAL, "fp_centroid_outliers: the embeddings hold a value that is not finite");
-    }
-    ++co[CO_CHUNKS];
-    co[CO_NARROWED] += rc == 1;
-    if (rc == 1 && h_chk[4] != 0) {   // a token met more than ASSIGN_CAP near-tied centroids: the whole chunk goes through the exact kernel
-      ++co[CO_FALLBACK];
-      if (fpk_assign_l2_exact(emb_d, n, cent_d, hn_d, C, dim, labels, st)) {
-        cleanup();
-        return fail(FP_EUNSUPPORTED, "fp_centroid_outliers: assignment chunk");
-      }
-    }
-    OCHK(hipEventRecord(ev[2], st));
-    fpk_outliers_chunk(emb_d, n, t0, cent_d, C, dim, hn_d, labels, threshold_sq, static_cast<float*>(d_sq), static_cast<int64_t*>(d_near),
-                       static_cast<uint8_t*>(d_flag), static_cast<int32_t*>(d_tcnt), static_cast<int32_t*>(d_toff),
-                       reinterpret_cast<int32_t*>(stat + 9), static_cast<int64_t*>(d_rows), st);
-    OCHK(hipEventRecord(ev[3], st));
-    int32_t h_cnt = 0;
-    OCHK(hipMemcpyAsync(&h_cnt, stat + 9, 4, hipMemcpyDeviceToHost, st));
-    OCHK(hipStreamSynchronize(st));
-    OCHK(hipGetLastError());
-    if (h_cnt < 0 || h_cnt > n) {
-      cleanup();
-      return fail(FP_EHIP, "fp_centroid_outliers: outlier count outside the chunk");
-    }
-    if (h_cnt > 0) OCHK(hipMemcpyAsync(out_rows + total, d_rows, (size_t)h_cnt * 8, hipMemcpyDeviceToHost, st));
-    if (out_sqdist) OCHK(hipMemcpyAsync(out_sqdist + t0, d_sq, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    if (out_nearest) OCHK(hipMemcpyAsync(out_nearest + t0, d_near, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    OCHK(hipEventRecord(ev[4], st));
-    OCHK(hipStreamSynchronize(st));
-    total += h_cnt;
-    for (int s = 0; s < 4; ++s) {
-      float ms = 0.f;
-      OCHK(hipEventElapsedTime(&ms, ev[s], ev[s + 1]));
-      co[CO_US_UPLOAD + s] += (int64_t)(ms * 1000.f + 0.5f);
-    }
-  }
-#undef OCHK
-  cleanup();
-  *out_count = total;
-  for (int i = 0; i < CO_N; ++i) g_co[i] = co[i];
-  g_co_have = 1;
   return FP_OK;
 }
 
@@ -2478,14 +2020,14 @@ struct fp_shard_ctx {
 
 extern "C" int fp_shard_begin(const fp_index* cix, const uint16_t* queries, int32_t nq, int32_t Q, int32_t dim,
                               const fp_search_params* p, fp_shard_ctx** out) {
-  if (!out) return fail(FP_EINVAL, "null argument");
+  if (!out) return fp_fail(FP_EINVAL, "null argument");
   *out = nullptr;
   if (int rc = validate_search(cix, nq, Q, dim, p)) return rc;
   fp_index* ix = const_cast<fp_index*>(cix);
-  if (nq < 1) return fail(FP_EINVAL, "need at least one query");
+  if (nq < 1) return fp_fail(FP_EINVAL, "need at least one query");
   HIPCHK(fp_set_device(ix->device));
   Scratch* s = acquire(ix);
-  if (!s) return fail(FP_EHIP, "could not create a HIP stream");
+  if (!s) return fp_fail(FP_EHIP, "could not create a HIP stream");
   fp_shard_ctx* c = new fp_shard_ctx();
   c->ix = ix; c->s = s; c->params = *p; c->B = nq; c->Q = Q;
   c->P = Pipe{};
@@ -2496,7 +2038,7 @@ extern "C" int fp_shard_begin(const fp_index* cix, const uint16_t* queries, int3
   if (e != hipSuccess) {
     release(ix, s);
     delete c;
-    return fail(FP_EHIP, hipGetErrorString(e));
+    return fp_fail(FP_EHIP, hipGetErrorString(e));
   }
   *out = c;
   return FP_OK;
@@ -2512,7 +2054,7 @@ extern "C" void fp_shard_end(fp_shard_ctx* c) {
 }
 
 extern "C" int fp_shard_stage1(fp_shard_ctx* c, void* dev_rec1) {
-  if (!c || !dev_rec1) return fail(FP_EINVAL, "null argument");
+  if (!c || !dev_rec1) return fp_fail(FP_EINVAL, "null argument");
   HIPCHK(fp_set_device(c->ix->device));
   Scratch* s = c->s;
   const int64_t R = c->P.sh.R;
@@ -2533,14 +2075,14 @@ extern "C" int fp_shard_stage1(fp_shard_ctx* c, void* dev_rec1) {
 }
 
 extern "C" int fp_shard_stage2(fp_shard_ctx* c, const void* dev_all_rec1, int32_t G, void* dev_rec2) {
-  if (!c || !dev_all_rec1 || !dev_rec2 || G < 1) return fail(FP_EINVAL, "bad argument");
+  if (!c || !dev_all_rec1 || !dev_rec2 || G < 1) return fp_fail(FP_EINVAL, "bad argument");
   HIPCHK(fp_set_device(c->ix->device));
   Scratch* s = c->s;
   const FpIndexDev& D = c->ix->d;
   const int64_t R = c->P.sh.R;
   const int B = c->B;
   if (fpk_shard_global_cut(dev_all_rec1, G, B, R, D.pid_offset, D.pid_offset + D.N, s->sel_pid.as<int32_t>(), s->sel_cnt.as<int32_t>(), s->st))
-    return fail(FP_EUNSUPPORTED, "n_ranks * max(n_full_scores/4, 1) is too large for the LDS cut of the sharded search (limit 16384 entries)");
+    return fp_fail(FP_EUNSUPPORTED, "n_ranks * max(n_full_scores/4, 1) is too large for the LDS cut of the sharded search (limit 16384 entries)");
   HIPCHK(s->exact.ensure((size_t)B * R * 4));
   if (!c->empty_all) {
     // MFMA scores + uncertainties (what the unsharded search ranks by); the near-tied documents are repaired in stage 3, once
@@ -2584,7 +2126,7 @@ static int shard_mark_and_repair(fp_index* ix, Scratch* s, const FpSearchShape& 
   float* u_unc = u_score + (size_t)2 * B * R;
   float* u_uncm = u_score + (size_t)3 * B * R;
   if (fpk_shard_union(all_rec2, G, B, R, s->tmpp.as<int64_t>(), u_score, u_src, u_unc, u_uncm, s->u_cnt.as<int32_t>(), st))
-    return fail(FP_EUNSUPPORTED, "n_ranks * max(n_full_scores/4, 1) is too large for the LDS merge of the sharded search (limit 16384 entries)");
+    return fp_fail(FP_EUNSUPPORTED, "n_ranks * max(n_full_scores/4, 1) is too large for the LDS merge of the sharded search (limit 16384 entries)");
   s->sh_marks_mode = 0;   // 0 nothing to exchange, 1 near-tied documents (marks), 2 every flagged document
   if (maxsim_repair_mode() != 0) {
     s->sh_marks_mode = (maxsim_repair_mode() != 2 && fpk_final_mark(u_score, u_unc, u_uncm, s->u_cnt.as<int32_t>(), R, B, K, s->ms_marks.as<int32_t>(),
@@ -2618,8 +2160,8 @@ static int shard_apply_and_rank(Scratch* s, const FpSearchShape& sh, const float
   char* od = s->out_all.as<char>();
   if (const int trc = fpk_final_topk(u_score, nullptr, s->tmpp.as<int64_t>(), s->u_cnt.as<int32_t>(), R, B, K, 0, reinterpret_cast<int64_t*>(od),
                                      reinterpret_cast<float*>(od + ol.score_off), reinterpret_cast<int32_t*>(od + ol.cnt_off), st))
-    return trc < 0 ? fail(FP_EUNSUPPORTED, "n_queries * n_ranks * max(n_full_scores / 4, 1) >= 2^31 in the final ranking of the union")
-                   : fail(FP_EHIP, "final ranking of the union failed (hip error " + std::to_string(trc) + ")");
+    return trc < 0 ? fp_fail(FP_EUNSUPPORTED, "n_queries * n_ranks * max(n_full_scores / 4, 1) >= 2^31 in the final ranking of the union")
+                   : fp_fail(FP_EHIP, "final ranking of the union failed (hip error " + std::to_string(trc) + ")");
   LAUNCHCHK("sharded merge");
   HIPCHK(hipMemcpyAsync(s->h_out.p, od, ol.total, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -2628,7 +2170,7 @@ static int shard_apply_and_rank(Scratch* s, const FpSearchShape& sh, const float
 }
 
 extern "C" int fp_shard_stage3(fp_shard_ctx* c, const void* dev_all_rec2, int32_t G, int32_t rank, void* dev_x) {
-  if (!c || !dev_all_rec2 || !dev_x || G < 1 || rank < 0 || rank >= G) return fail(FP_EINVAL, "bad argument");
+  if (!c || !dev_all_rec2 || !dev_x || G < 1 || rank < 0 || rank >= G) return fp_fail(FP_EINVAL, "bad argument");
   HIPCHK(fp_set_device(c->ix->device));
   Scratch* s = c->s;
   if (c->params.top_k == 0) return FP_OK;
@@ -2639,7 +2181,7 @@ extern "C" int fp_shard_stage3(fp_shard_ctx* c, const void* dev_all_rec2, int32_
 }
 
 extern "C" int fp_shard_stage4(fp_shard_ctx* c, const void* dev_all_x, int32_t G, int64_t* out_pids, float* out_scores, int32_t* out_counts) {
-  if (!c || !dev_all_x || G < 1 || !out_counts) return fail(FP_EINVAL, "bad argument");
+  if (!c || !dev_all_x || G < 1 || !out_counts) return fp_fail(FP_EINVAL, "bad argument");
   HIPCHK(fp_set_device(c->ix->device));
   for (int i = 0; i < c->B; ++i) out_counts[i] = 0;
   if (c->params.top_k == 0) return FP_OK;
@@ -2687,7 +2229,7 @@ static RcclApi* rccl_api() {
 }
 static int rccl_fail(const char* what, int rc) {
   RcclApi* a = rccl_api();
-  return fail(FP_EHIP, std::string("RCCL: ") + what + " failed: " + ((a && a->GetErrorString) ? a->GetErrorString(rc) : "error ") + " (" + std::to_string(rc) + ")");
+  return fp_fail(FP_EHIP, std::string("RCCL: ") + what + " failed: " + ((a && a->GetErrorString) ? a->GetErrorString(rc) : "error ") + " (" + std::to_string(rc) + ")");
 }
 
 struct fp_comm {
@@ -2696,9 +2238,9 @@ struct fp_comm {
 };
 
 extern "C" int fp_comm_unique_id(void* out_id_128) {
-  if (!out_id_128) return fail(FP_EINVAL, "null argument");
+  if (!out_id_128) return fp_fail(FP_EINVAL, "null argument");
   RcclApi* a = rccl_api();
-  if (!a) return fail(FP_EUNSUPPORTED, "RCCL unavailable: librccl could not be loaded (set FP_RCCL_LIB)");
+  if (!a) return fp_fail(FP_EUNSUPPORTED, "RCCL unavailable: librccl could not be loaded (set FP_RCCL_LIB)");
   FpNcclUid id;
   if (int rc = a->GetUniqueId(&id)) return rccl_fail("ncclGetUniqueId", rc);
   memcpy(out_id_128, &id, sizeof(id));
@@ -2706,10 +2248,10 @@ extern "C" int fp_comm_unique_id(void* out_id_128) {
 }
 
 extern "C" int fp_comm_create(int device_id, int n_ranks, int rank, const void* unique_id_128, fp_comm** out) {
-  if (!out || !unique_id_128 || n_ranks < 1 || rank < 0 || rank >= n_ranks) return fail(FP_EINVAL, "bad argument");
+  if (!out || !unique_id_128 || n_ranks < 1 || rank < 0 || rank >= n_ranks) return fp_fail(FP_EINVAL, "bad argument");
   *out = nullptr;
   RcclApi* a = rccl_api();
-  if (!a) return fail(FP_EUNSUPPORTED, "RCCL unavailable: librccl could not be loaded (set FP_RCCL_LIB)");
+  if (!a) return fp_fail(FP_EUNSUPPORTED, "RCCL unavailable: librccl could not be loaded (set FP_RCCL_LIB)");
   HIPCHK(fp_set_device(device_id));
   FpNcclUid id;
   memcpy(&id, unique_id_128, sizeof(id));
@@ -2791,7 +2333,7 @@ static int shard_search_batch(fp_index* ix, Scratch* s, fp_comm* comm, RcclApi* 
       if (e == hipSuccess) e = hipMemcpyAsync(s->qin.p, queries, (size_t)B * Q * D.dim * 2, hipMemcpyHostToDevice, st);
       if (e != hipSuccess) {
         if (api->CommAbort && comm->comm) { (void)api->CommAbort(comm->comm); comm->comm = nullptr; }
-        return fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e) + " (sharded search buffers; the communicator was aborted)");
+        return fp_fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e) + " (sharded search buffers; the communicator was aborted)");
       }
     }
     int32_t* d_flags = s->spec_total.as<int32_t>() + 2;   // (behind the 8 bytes of the candidate total)
@@ -2799,7 +2341,7 @@ static int shard_search_batch(fp_index* ix, Scratch* s, fp_comm* comm, RcclApi* 
     static const int fail_at = (int)fp_test_opt("shard_fail_at", 0);   // testing: a local failure in stage n
     // ---- front half (S1..S5 on the shard) ----
     bool have_front = false;
-    if (fail_at == 1) note(fail(FP_EHIP, "injected failure in the front half (FP_SHARD_FAIL_AT=1)"));
+    if (fail_at == 1) note(fp_fail(FP_EHIP, "injected failure in the front half (FP_SHARD_FAIL_AT=1)"));
     else if (!empty_local) {
       s->fold_stats = false;
       const int rc = run_front(P, nullptr, nullptr, false);
@@ -2814,12 +2356,12 @@ static int shard_search_batch(fp_index* ix, Scratch* s, fp_comm* comm, RcclApi* 
     fpk_shard_status(s->sh_all.p, G, (int64_t)B * R * 16, 12, d_flags, st);
     // global cut on the union (sort in LDS, or select + ordered compaction when n_ranks * R is beyond it)
     if (fpk_shard_global_cut(s->sh_all.p, G, B, R, D.pid_offset, D.pid_offset + D.N, s->sel_pid.as<int32_t>(), s->sel_cnt.as<int32_t>(), st)) {
-      note(fail(FP_EUNSUPPORTED, "n_ranks * max(n_full_scores/4, 1) does not fit a 32-bit union index"));
+      note(fp_fail(FP_EUNSUPPORTED, "n_ranks * max(n_full_scores/4, 1) does not fit a 32-bit union index"));
       (void)hipMemsetAsync(s->sel_cnt.p, 0, (size_t)B * 4, st);
     }
     // exchange 2: MFMA scores + uncertainties of the local survivors
     bool have_scores = false;
-    if (fail_at == 2) note(fail(FP_EHIP, "injected failure before the MaxSim pass (FP_SHARD_FAIL_AT=2)"));
+    if (fail_at == 2) note(fp_fail(FP_EHIP, "injected failure before the MaxSim pass (FP_SHARD_FAIL_AT=2)"));
     if (have_front && !(status & SH_FAILED)) {
       const int rc = run_maxsim(ix, s, P.sh, R, K, 0);
       note(rc);
@@ -2834,7 +2376,7 @@ static int shard_search_batch(fp_index* ix, Scratch* s, fp_comm* comm, RcclApi* 
     // exchange 3: the union and its near-tie marking are identical on every rank; each rank repairs the marked documents it holds
     // and ships their scores ([B][R] floats by union position)
     (void)hipMemsetAsync(s->sh_x.p, 0, (size_t)xstride * 4, st);
-    if (fail_at == 3) note(fail(FP_EHIP, "injected failure before the marking (FP_SHARD_FAIL_AT=3)"));
+    if (fail_at == 3) note(fp_fail(FP_EHIP, "injected failure before the marking (FP_SHARD_FAIL_AT=3)"));
     note(shard_mark_and_repair(ix, s, P.sh, s->sh_all.p, G, comm->rank, !have_scores, K, s->sh_x.as<float>(), st));
     if (shard_marks_mode(R) != 0) {   // (the same on every rank whatever happened locally: a function of the environment and R)
       (void)hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s->sh_x.as<int32_t>() + (int64_t)B * R), status, 1, st);
@@ -2845,16 +2387,16 @@ static int shard_search_batch(fp_index* ix, Scratch* s, fp_comm* comm, RcclApi* 
     (void)hipMemcpyAsync(static_cast<char*>(s->h_small.p) + 40, d_flags, 4, hipMemcpyDeviceToHost, st);
     const int mrc = (status & SH_FAILED) ? FP_OK : shard_apply_and_rank(s, P.sh, s->sh_xall.as<float>(), K, out_pids, out_scores, out_counts, st, xstride);
     if (hipError_t se = hipStreamSynchronize(st); se != hipSuccess)
-      return leave(fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(se) + " (sharded search; the communicator was aborted)"));
+      return leave(fp_fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(se) + " (sharded search; the communicator was aborted)"));
     const bool late_err = [&] {   // an error that surfaced behind the last exchange: the peers have not heard of it
-      if (hipError_t le = hipGetLastError(); le != hipSuccess) { (void)fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(le) + " (sharded search)"); return true; }
+      if (hipError_t le = hipGetLastError(); le != hipSuccess) { (void)fp_fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(le) + " (sharded search)"); return true; }
       return false;
     }();
     const int flags = *reinterpret_cast<const int32_t*>(static_cast<const char*>(s->h_small.p) + 40);
-    if (status & SH_FAILED) return fail(FP_EHIP, "fp_shard_search failed on this rank (every rank reports the batch as failed): " + first_err);
+    if (status & SH_FAILED) return fp_fail(FP_EHIP, "fp_shard_search failed on this rank (every rank reports the batch as failed): " + first_err);
     if (flags & SH_FAILED) {
       for (int i = 0; i < B; ++i) out_counts[i] = 0;
-      return fail(FP_EHIP, "fp_shard_search: another rank failed during this batch (its error is reported there); no rank returns results");
+      return fp_fail(FP_EHIP, "fp_shard_search: another rank failed during this batch (its error is reported there); no rank returns results");
     }
     // every rank saw the same status words: an overflow anywhere -> EVERY rank goes round again, whatever its own merge did with
     // the discarded attempt (a rank that returned here instead would leave the others alone in attempt 1's collectives)
@@ -2869,23 +2411,23 @@ static int shard_search_batch(fp_index* ix, Scratch* s, fp_comm* comm, RcclApi* 
     if (have_front) learn_capacity(s, *reinterpret_cast<const int64_t*>(s->h_small.p));
     return FP_OK;
   }
-  return fail(FP_EHIP, "fp_shard_search: the candidate capacity overflowed twice");
+  return fp_fail(FP_EHIP, "fp_shard_search: the candidate capacity overflowed twice");
 }
 
 extern "C" int fp_shard_search(const fp_index* cix, fp_comm* comm, const uint16_t* queries, int32_t nq, int32_t Q, int32_t dim,
                                const fp_search_params* p, int64_t* out_pids, float* out_scores, int32_t* out_counts) {
-  if (!comm || !comm->comm) return fail(FP_EINVAL, "null (or aborted) communicator");
+  if (!comm || !comm->comm) return fp_fail(FP_EINVAL, "null (or aborted) communicator");
   if (int rc = validate_search(cix, nq, Q, dim, p)) return rc;
-  if (nq < 1 || !queries || !out_counts || (p->top_k > 0 && (!out_pids || !out_scores))) return fail(FP_EINVAL, "bad argument");
+  if (nq < 1 || !queries || !out_counts || (p->top_k > 0 && (!out_pids || !out_scores))) return fp_fail(FP_EINVAL, "bad argument");
   RcclApi* api = rccl_api();
-  if (!api) return fail(FP_EUNSUPPORTED, "RCCL unavailable");
+  if (!api) return fp_fail(FP_EUNSUPPORTED, "RCCL unavailable");
   fp_index* ix = const_cast<fp_index*>(cix);
-  if (ix->device != comm->device) return fail(FP_EINVAL, "index and communicator live on different devices");
+  if (ix->device != comm->device) return fp_fail(FP_EINVAL, "index and communicator live on different devices");
   HIPCHK(fp_set_device(ix->device));
   for (int i = 0; i < nq; ++i) out_counts[i] = 0;
   if (p->top_k == 0) return FP_OK;
   Scratch* s = acquire(ix);
-  if (!s) return fail(FP_EHIP, "could not create a HIP stream");
+  if (!s) return fp_fail(FP_EHIP, "could not create a HIP stream");
   struct Rel { fp_index* ix; Scratch* s; ~Rel() { (void)hipStreamSynchronize(s->st); release(ix, s); } } rel{ix, s};
   // Sub-batches against a FIXED budget of the centroid-score table (every rank must split the batch identically, so the budget
   // may not depend on a rank's free memory as fp_search's does): 16 GiB, FP_SHARD_S_BUDGET_KB for tests
@@ -2908,7 +2450,7 @@ extern "C" int fp_shard_search(const fp_index* cix, fp_comm* comm, const uint16_
 // exhaustive arithmetic self-test (see fp_index_ops.hip k_selftest_arith)
 // ------------------------------------------------------------------------------------------
 extern "C" int fp_selftest_arith(int device_id, uint64_t* out_mismatches /*[16]*/) {
-  if (!out_mismatches) return fail(FP_EINVAL, "null argument");
+  if (!out_mismatches) return fp_fail(FP_EINVAL, "null argument");
   HIPCHK(fp_set_device(device_id));
   unsigned long long* d = nullptr;
   HIPCHK(hipMalloc((void**)&d, 128));
@@ -2917,7 +2459,7 @@ extern "C" int fp_selftest_arith(int device_id, uint64_t* out_mismatches /*[16]*
   fpk_selftest_arith(d, us);
   hipError_t e = copy_sync(out_mismatches, d, 128, hipMemcpyDeviceToHost, us);
   (void)hipFree(d);
-  if (e != hipSuccess) return fail(FP_EHIP, hipGetErrorString(e));
+  if (e != hipSuccess) return fp_fail(FP_EHIP, hipGetErrorString(e));
   return FP_OK;
 }
 
@@ -2928,13 +2470,13 @@ extern "C" int64_t fp_index_ivf_total(const fp_index* ix) {
   if (!ix || !ix->has_ivf) return 0;
   (void)fp_set_device(ix->device);
   int64_t tot = 0;
-  if (copy_sync(&tot, ix->d.ivf_off + ix->d.P, 8, hipMemcpyDeviceToHost, util_stream(ix->device)) != hipSuccess) return fail(FP_EHIP, "memcpy");
+  if (copy_sync(&tot, ix->d.ivf_off + ix->d.P, 8, hipMemcpyDeviceToHost, util_stream(ix->device)) != hipSuccess) return fp_fail(FP_EHIP, "memcpy");
   return tot;
 }
 
 extern "C" int fp_index_export(const fp_index* ix, int64_t* doc_codes, uint8_t* doc_residuals, int64_t* doc_lengths, int64_t* ivf,
                                int32_t* ivf_lengths) {
-  if (!ix) return fail(FP_EINVAL, "null argument");
+  if (!ix) return fp_fail(FP_EINVAL, "null argument");
   HIPCHK(fp_set_device(ix->device));
   const FpIndexDev& D = ix->d;
   if (doc_lengths)

@@ -1,5 +1,6 @@
 // Internal declarations shared by the HIP kernels (fp_kernels.hip, fp_index_ops.hip, fp_token_scores.hip, fp_kmeans.hip, fp_outliers.hip, fp_maxsim.hip, fp_synth.hip) and the
-// host engine (fp_engine.cpp).  Not part of the C ABI (see include/fastplaid.h).
+// host files (fp_engine.cpp: the search engine; fp_build.cpp: the stand-alone index-build operators).  Not part of the C ABI (see
+// include/fastplaid.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdlib>
@@ -416,6 +417,7 @@ void fpk_shard_apply3(const int32_t* marks, const int32_t* nmark, const float* u
 // misc
 void fpk_narrow_i64_i32(const int64_t* in, int32_t* out, int64_t n, int64_t add, hipStream_t st, int64_t limit = 0, uint32_t* bad = nullptr);
 void fpk_ivf_check_sorted(const int64_t* off, const int32_t* pids, int64_t P, uint32_t* flag, hipStream_t st);
+// (from here to fpk_outliers_chunk: the index-build launchers, called by the operators of fp_build.cpp)
 // create.rs:148-184, :404-428 on device pointers: nearest centroid (MFMA narrowing + exact re-check of the near-ties, or the exact
 // kernel alone; codes32 scratch, codes64 output) + quantised packed residuals.  cmaxabs = max |centroid element| (bounds the MFMA
 // summation error); work = fpk_compress_work_bytes(T) bytes of device scratch (nullptr: exact kernel only).  dim: [1, 256] or a
@@ -437,7 +439,7 @@ int fpk_assign_l2_exact(const uint16_t* emb, int64_t T, const uint16_t* cent, co
 // {max|cent|, max half_sqnorm} as fp32 bits; work = fpk_compress_work_bytes(T); 1: narrowed, *overflow to be read by the caller
 int fpk_assign_l2_narrow(const uint16_t* emb, int64_t T, const uint16_t* cent, const float* half_sqnorm, const uint32_t* stat, int64_t C, int D,
                          int32_t* codes32, void* work, int32_t* overflow, hipStream_t st);
-// ---- fp_kmeans.hip: the Lloyd update on the device (fp_kmeans, include/fastplaid.h) ------------
+// ---- fp_kmeans.hip: the Lloyd update on the device (fp_kmeans of fp_build.cpp, include/fastplaid.h) ------------
 // value of an fp16 bit pattern in units of 2^-24 (every finite fp16 value is such an integer; |v| < 2^40)
 static inline __host__ __device__ int64_t fp_f16_fixed(uint16_t h) {
   const int e = (h >> 10) & 31, m = h & 0x3FF;
@@ -456,7 +458,7 @@ void fpk_km_index(const int32_t* labels, int64_t n, int64_t K, int32_t* cnt, int
 void fpk_km_sum(const uint16_t* data, int64_t n, int D, int64_t K, const int32_t* labels, const int32_t* members, int64_t* sums,
                 hipStream_t st);
 void fpk_km_widen_counts(const int32_t* cnt, int64_t* out, int64_t K, hipStream_t st);
-// ---- fp_outliers.hip: fp_centroid_outliers (include/fastplaid.h) around the assignment ---------
+// ---- fp_outliers.hip: fp_centroid_outliers (fp_build.cpp, include/fastplaid.h) around the assignment ---------
 // half_sqnorm[c] = 0.5f * ascending-d chain of cent[c][d]^2, stat = {max|cent|, max half_sqnorm} as fp32 bits (zeroed here)
 void fpk_out_prepare(const uint16_t* cent, int64_t C, int D, float* half_sqnorm, uint32_t* stat, hipStream_t st);
 // one chunk with its labels (all in [0, C)): sqdist [T], nearest [T] (nullable) = the labels widened, flag [T] and tilecnt / tileoff
