@@ -1,9 +1,10 @@
 // Host engine + C ABI (include/fastplaid.h) of the MI355X PLAID search library.
 // Replaces, for the search path, rust/search/{search,load,tensor,padding}.rs and
-// rust/utils/residual_codec.rs of the reference: index construction = upload + re-layout,
+// rust/utils/residual_codec.rs of the reference:
 // search_many = one batched, stream-ordered pipeline of HIP kernels (fp_kernels.hip, fp_maxsim.hip).
-// The stand-alone index-build operators (fp_compress, fp_assign_l2, fp_kmeans, fp_centroid_outliers) are in fp_build.cpp; what
-// the two files share is declared in fp_host.h and defined here.
+// The life of an fp_index (index construction = upload + re-layout, destruction, getters, read-back) is in fp_index.cpp, the
+// stand-alone index-build operators (fp_compress, fp_assign_l2, fp_kmeans, fp_centroid_outliers) are in fp_build.cpp; what the
+// three files share is declared in fp_host.h and defined here.
 // No torch / tch; only the HIP runtime.
 #include <atomic>
 #include "../../include/fastplaid.h"
@@ -65,7 +66,7 @@ static std::atomic<uint64_t> g_graph_replays{0};   // fp_graph_replay_count(): c
 // fp_set_graph_replay / FP_GRAPH: on unless the environment says 0
 static std::atomic<int> g_graph_replay{[] { const char* e = getenv("FP_GRAPH"); return (e && atoi(e) == 0) ? 0 : 1; }()};
 // (DevBuf and HostBuf below free themselves and are not copyable: they are members of a Scratch, and deleting the scratch -- with
-// its index's device selected, fp_index_destroy -- frees every one of them)
+// its index's device selected, ~fp_index -- frees every one of them)
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
@@ -119,7 +120,7 @@ hipError_t fp_set_device(int device) {
 // The library never touches the legacy (null) stream (one exception: prepay_legacy_stream): a synchronous hipMemcpy there is refused -- and invalidates the capture --
 // while another thread of the process captures a graph (fp_search does, on its scratch's stream).  Blocking copies go through
 // an explicit stream instead: the caller's own (index construction, a scratch) or this per-device utility stream.
-static hipStream_t util_stream(int device) {
+hipStream_t util_stream(int device) {
   static std::mutex mu;
   static hipStream_t streams[64] = {};
   std::lock_guard<std::mutex> g(mu);
@@ -133,7 +134,7 @@ static std::atomic<int> g_open_captures{0};
 // stream (a hardware queue: 3 - 4 ms) the first time something needs it, and the first hipGraphInstantiate of a process does -- ~9 ms
 // inside somebody's third fp_search call (profiles/r06_first_graph_cost.txt).  Index construction is where a few milliseconds do not
 // matter.  Skipped while one of the library's own captures is open (the runtime would refuse the call and invalidate that capture).
-static void prepay_legacy_stream() {
+void prepay_legacy_stream() {
   if (g_open_captures.load(std::memory_order_acquire) != 0) return;
   void* p = nullptr;
   if (hipMalloc(&p, 64) == hipSuccess) {
@@ -142,7 +143,7 @@ static void prepay_legacy_stream() {
   }
   (void)hipGetLastError();
 }
-static hipError_t copy_sync(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t st) {
+hipError_t copy_sync(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t st) {
   if (bytes == 0) return hipSuccess;
   const hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, st);
   return e != hipSuccess ? e : hipStreamSynchronize(st);
@@ -275,31 +276,17 @@ struct Scratch : ScratchGen {
   int l0_poor = 0;              // consecutive batches in which level 0 let more than a quarter of the candidates through
   int l0h_poor = 0;             // ... and its hot-code form
   int sh_marks_mode = 0;        // sharded search, third exchange: 0 none, 1 near-tied documents, 2 every flagged document
-  // the graph executables, events and stream; the buffers free themselves when the scratch is deleted
-  void destroy() {
-    if (graph.exec) { (void)hipGraphExecDestroy(graph.exec); graph.exec = nullptr; graph.valid = false; }
+  // the graph executables, events and stream; the buffers free themselves after this body
+  ~Scratch() {
+    if (graph.exec) (void)hipGraphExecDestroy(graph.exec);
     for (auto& sh2 : shapes)
-      if (sh2.graph.exec) { (void)hipGraphExecDestroy(sh2.graph.exec); sh2.graph.exec = nullptr; }
+      if (sh2.graph.exec) (void)hipGraphExecDestroy(sh2.graph.exec);
     for (auto& e : ev)
       if (e) (void)hipEventDestroy(e);
     if (st) (void)hipStreamDestroy(st);
   }
 };
-
-struct fp_index {
-  FpIndexDev d{};
-  int device = 0;
-  bool has_ivf = false;
-  std::vector<void*> owned;
-  std::vector<int64_t> h_doc_off;
-  int64_t bytes = 0;
-  std::mutex mu;
-  std::vector<Scratch*> pool;
-  bool synthetic = false;
-  int64_t n_hard_tokens = 0;   // tokens without a one-multiply reciprocal (k_token_rinv)
-  float cent_norm_max = 1.f;   // largest centroid norm (>= 1): scales S1's certification window (FpS1Exact)
-  bool tickets_ok = true;      // the fence-free ticket chains passed their self-test on this index's device (finish_layout)
-};
+void fp_delete_scratch(Scratch* s) { delete s; }
 
 static thread_local float g_last_ms[ST_N];
 static thread_local bool g_have_ms = false;
@@ -378,470 +365,24 @@ static void release(fp_index* ix, Scratch* s) {
   std::lock_guard<std::mutex> g(ix->mu);
   ix->pool.push_back(s);
 }
-
-// ------------------------------------------------------------------------------------------
-// index construction (load.rs:124-186)
-// ------------------------------------------------------------------------------------------
-static void build_lut_host(int nbits, const uint16_t* weights, std::vector<uint16_t>& lut) {
-  // residual_codec.rs:83-140 folded: byte -> rev_map -> idx_lookup[rev][j] -> weights
-  const int per = 8 / nbits, mask = (1 << nbits) - 1;
-  lut.assign((size_t)256 * per, 0);
-  for (int v = 0; v < 256; ++v) {
-    unsigned out = 0;
-    int pos = 8;
-    while (pos >= nbits) {
-      unsigned seg = ((unsigned)v >> (pos - nbits)) & (unsigned)mask, rev = 0;
-      for (int k = 0; k < nbits; ++k)
-        if (seg & (1u << k)) rev |= 1u << (nbits - 1 - k);
-      out |= rev;
-      if (pos > nbits) out <<= nbits;
-      pos -= nbits;
-    }
-    out &= 0xFF;
-    int j = 0;
-    for (int k = per - 1; k >= 0; --k) lut[(size_t)v * per + j++] = weights[(out >> (k * nbits)) & mask];
+// a scratch taken from the index's pool for the length of one call (s is null when no stream could be created) and given back
+// on every way out.  The staged shard API, whose scratch lives from fp_shard_begin to fp_shard_end, acquires and releases itself.
+struct FP_HIDDEN Lease {
+  enum Return { kPlain, kAbandonCapture /*an error return in the middle of a capture: close it, or the stream stays unusable*/,
+                kSyncFirst /*work may still be enqueued on the stream*/ };
+  fp_index* const ix;
+  Scratch* const s;
+  const Return how;
+  explicit Lease(fp_index* ix_, Return how_ = kPlain) : ix(ix_), s(acquire(ix_)), how(how_) {}
+  Lease(const Lease&) = delete;
+  Lease& operator=(const Lease&) = delete;
+  ~Lease() {
+    if (!s) return;
+    if (how == kAbandonCapture && s->capturing) abandon_capture(s);
+    if (how == kSyncFirst) (void)hipStreamSynchronize(s->st);
+    release(ix, s);
   }
-}
-
-// largest row norm of an fp16 matrix (never below 1): the rounding noise of a score's fp32 chain scales with |c| |q|
-static float max_row_norm_f16(const uint16_t* m, int64_t rows, int dim) {
-  double best = 1.0;
-  for (int64_t r = 0; r < rows; ++r) {
-    double ss = 0.0;
-    const uint16_t* row = m + r * dim;
-    for (int k = 0; k < dim; ++k) {
-      const double x = (double)(float)__builtin_bit_cast(_Float16, row[k]);
-      ss += x * x;
-    }
-    if (ss > best * best) best = std::sqrt(ss);
-  }
-  return (float)best;
-}
-
-template <typename T>
-static hipError_t dev_alloc(fp_index* ix, T** p, size_t n) {
-  void* q = nullptr;
-  size_t bytes = (n ? n : 1) * sizeof(T) + 64;  // slack: vector loads may touch past the end
-  hipError_t e = hipMalloc(&q, bytes);
-  if (e != hipSuccess) return e;
-  ix->owned.push_back(q);
-  ix->bytes += (int64_t)bytes;
-  *p = reinterpret_cast<T*>(q);
-  return hipSuccess;
-}
-
-// limit > 0: every entry must lie in [0, limit) -- `what` names the array in the error (the reference fails on such an index
-// inside index_select, per query; a code that is no centroid or a list entry that is no document would be an out-of-bounds
-// read on the device here, so the index is refused when it is built)
-static int upload_narrow(const int64_t* host, int32_t* dev, int64_t n, hipStream_t st, int64_t limit = 0, const char* what = "") {
-  // chunked i64 -> i32 through a device staging buffer
-  if (n <= 0) return FP_OK;
-  const int64_t chunk = 32ll << 20;  // 32M entries = 256 MiB
-  int64_t* stage = nullptr;
-  const size_t stage_bytes = (size_t)std::min(chunk, n) * 8;
-  HIPCHK(hipMalloc((void**)&stage, stage_bytes + 8));
-  uint32_t* bad = limit > 0 ? reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(stage) + stage_bytes) : nullptr;
-  uint32_t h_bad = 0;
-  hipError_t e = bad ? hipMemsetAsync(bad, 0, 4, st) : hipSuccess;
-  for (int64_t s = 0; s < n && e == hipSuccess; s += chunk) {
-    int64_t m = std::min(chunk, n - s);
-    e = hipMemcpyAsync(stage, host + s, (size_t)m * 8, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) break;
-    fpk_narrow_i64_i32(stage, dev + s, m, 0, st, limit, bad);
-    e = hipStreamSynchronize(st);
-  }
-  if (e == hipSuccess && bad) e = copy_sync(&h_bad, bad, 4, hipMemcpyDeviceToHost, st);
-  (void)hipFree(stage);
-  if (e != hipSuccess) return fp_fail(FP_EHIP, hipGetErrorString(e));
-  if (h_bad) return fp_fail(FP_EINVAL, std::string(what) + ": " + std::to_string(h_bad) + " entries outside [0, " + std::to_string(limit) + ")");
-  return FP_OK;
-}
-
-// residual_codec.rs:83-140 / search.rs:53-107 are generic in nbits (a divisor of 8) and dim; the centroid GEMM stages K in
-// 8-dim (16-byte) pieces, hence dim % 8.  Every accepted shape has an MFMA MaxSim kernel: fixed-dim ones for thirteen shapes
-// (k_maxsim6 / k_maxsim5), the K-sliced k_maxsim_sl at a runtime dim for the rest.
-static int check_shape(int nbits, int dim) {
-  if (!(nbits == 1 || nbits == 2 || nbits == 4 || nbits == 8)) return fp_fail(FP_EINVAL, "nbits must divide 8 (1, 2, 4 or 8)");
-  if (dim < 8 || dim % 8 != 0 || dim > 1024) return fp_fail(FP_EUNSUPPORTED, "dim must be a multiple of 8 in [8, 1024]");
-  return FP_OK;
-}
-
-struct StreamGuard {   // destroys the construction stream on every exit path
-  hipStream_t st = nullptr;
-  ~StreamGuard() { if (st) (void)hipStreamDestroy(st); }
 };
-
-// common tail of index construction: tokens sorted by code inside each document, per-token norms, per-document unique codes.
-// ix->d.{centroids, lut, codes, residuals, doc_off} are set.  Every device buffer is registered in ix->owned before its
-// producer's return code is looked at, so a failing build frees it with the index.
-// the self-test of the "last workgroup finishes the job" chains, once per device and process (fpk_ticket_selftest)
-static bool device_tickets_ok(int device, hipStream_t st) {
-  static std::mutex mu;
-  static int state[64];   // 0 unknown, 1 ok, 2 failed
-  std::lock_guard<std::mutex> g(mu);
-  int& s = state[device & 63];
-  if (s == 0) s = fpk_ticket_selftest(st) == 0 ? 1 : 2;
-  return s == 1;
-}
-
-static int finish_layout(fp_index* ix, int maxlen, hipStream_t st) {
-  FpIndexDev& D = ix->d;
-  ix->tickets_ok = device_tickets_ok(ix->device, st);
-  {
-    uint16_t* perm = nullptr;
-    const int src = fps_sort_docs(const_cast<int32_t*>(D.codes), const_cast<uint8_t*>(D.residuals), D.doc_off, D.N, D.T, maxlen, D.pr, &perm, st);
-    if (perm) { ix->owned.push_back(perm); ix->bytes += D.T * 2; }
-    if (src != 0) return fp_fail(FP_EHIP, "in-document token sort failed (hip error " + std::to_string(src) + ")");
-    D.perm = perm;
-  }
-  {
-    uint16_t* norms = nullptr;
-    hipError_t e = hipMalloc((void**)&norms, (size_t)std::max<int64_t>(D.T, 1) * 2 + 64);
-    if (e != hipSuccess) return fp_fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e) + " (token norms)");
-    ix->owned.push_back(norms);
-    ix->bytes += D.T * 2;
-    fpk_token_norms(D, norms, st);
-    e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fp_fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e) + " (token norms)");
-    D.norms = norms;
-  }
-  // S1's zero-padded view of the centroid table (FpIndexDev::cent_s1)
-  D.cent_s1 = nullptr;
-  D.dim_s1 = D.dim;
-  if (D.dim < 256 && D.dim != 64 && D.dim != 128) {
-    const int dp = D.dim < 64 ? 64 : (D.dim < 128 ? 128 : 256);
-    uint16_t* cp = nullptr;
-    hipError_t e = hipMalloc((void**)&cp, (size_t)D.C * dp * 2 + 64);
-    if (e != hipSuccess) return fp_fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e) + " (padded centroid table)");
-    ix->owned.push_back(cp);
-    ix->bytes += D.C * dp * 2;
-    e = hipMemsetAsync(cp, 0, (size_t)D.C * dp * 2, st);
-    if (e == hipSuccess) e = hipMemcpy2DAsync(cp, (size_t)dp * 2, D.centroids, (size_t)D.dim * 2, (size_t)D.dim * 2, (size_t)D.C, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fp_fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e) + " (padded centroid table)");
-    D.cent_s1 = cp;
-    D.dim_s1 = dp;
-  }
-  D.resid_native = 0;
-  D.rinv = nullptr;
-  if (fpk_maxsim6_shape(D.dim, D.nbits)) {
-    // per-token reciprocals (from the rows still in the reference's byte order), then every row rewritten in the MaxSim kernel's
-    // unit order IN PLACE, a slab of rows at a time through a bounded temporary
-    static const bool use_rinv = fp_test_opt("ms_rinv", 1) != 0;
-    hipError_t e = hipSuccess;
-    if (use_rinv) {
-      uint32_t* rv = nullptr;
-      unsigned long long* nh = nullptr;
-      e = hipMalloc((void**)&rv, (size_t)std::max<int64_t>(D.T, 1) * 4 + 64);
-      if (e != hipSuccess) return fp_fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e) + " (token reciprocals)");
-      ix->owned.push_back(rv);
-      ix->bytes += D.T * 4;
-      e = hipMalloc((void**)&nh, 8);
-      if (e != hipSuccess) return fp_fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e) + " (token reciprocals)");
-      ix->owned.push_back(nh);
-      (void)hipMemsetAsync(nh, 0, 8, st);
-      fpk_token_rinv(D, rv, nh, st);
-      unsigned long long hard = 0;
-      e = hipMemcpyAsync(&hard, nh, 8, hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess) e = hipStreamSynchronize(st);
-      if (e != hipSuccess) return fp_fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e) + " (token reciprocals)");
-      D.rinv = rv;
-      ix->n_hard_tokens = (int64_t)hard;
-    }
-    if (D.T > 0) {
-      const int64_t slab = std::max<int64_t>(1, std::min<int64_t>(D.T, (512ll << 20) / D.pr));
-      uint8_t* tmp = nullptr;
-      e = hipMalloc((void**)&tmp, (size_t)slab * D.pr);
-      if (e != hipSuccess) return fp_fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e) + " (native residual order)");
-      for (int64_t t0 = 0; t0 < D.T; t0 += slab) fpk_resid_native(D, t0, std::min<int64_t>(slab, D.T - t0), tmp, st);
-      e = hipStreamSynchronize(st);
-      (void)hipFree(tmp);
-      if (e != hipSuccess) return fp_fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e) + " (native residual order)");
-    }
-    D.resid_native = 1;
-  }
-  {
-    int64_t* uoff = nullptr; int32_t* ucodes = nullptr; int64_t U = 0;
-    hipError_t e = hipMalloc((void**)&uoff, ((size_t)D.N + 1) * 8 + 64);
-    if (e != hipSuccess) return fp_fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e) + " (unique-code offsets)");
-    ix->owned.push_back(uoff);
-    ix->bytes += (D.N + 1) * 8;
-    const int urc = fps_build_ucodes(D.codes, D.doc_off, D.N, maxlen, &ucodes, &U, uoff, st);
-    if (ucodes) { ix->owned.push_back(ucodes); ix->bytes += U * 4; }
-    if (urc != 0) return fp_fail(FP_EHIP, "unique-code build failed (hip error " + std::to_string(urc) + ")");
-    D.ucodes = ucodes; D.uoff = uoff; D.U = U;
-  }
-  // packed code lines for S4's level 0: one set per range of 2^17 centroids (codes relative to the range), up to 2^20
-  D.n_ranges = 0;
-  D.n_lines = 0;
-  D.l0_ppl = 8;
-  // the static part of run_front's level-0 predicate (table of >= 32768 centroids, documents of <= 64 distinct codes on average;
-  // FP_APPROX_IMPL=l0 forces level 0 in tests): an index that can never take level 0 does not carry the packed lines
-  static const bool l0_forced = [] { const char* e2 = getenv("FP_APPROX_IMPL"); return e2 && e2[0] == 'l'; }();
-  if (D.C <= 8 * (1ll << 17) && (l0_forced || (D.C * 64 >= (2ll << 20) && D.U <= 64 * D.N))) {
-    const int nr = (int)((D.C + (1ll << 17) - 1) >> 17);
-    // lines of 4 pieces (24 codes) when a document has few codes per range: half the lanes, half the bytes per candidate and range
-    static const int ppl_env = (int)fp_test_opt("l0_ppl", 0);
-    if (ppl_env == 4 || ppl_env == 8) D.l0_ppl = ppl_env;
-    else if (nr > 1 && D.N > 0 && (double)D.U / ((double)D.N * nr) <= 14.0) D.l0_ppl = 4;
-    // several ranges: ONE array of first lines, a document's ranges side by side (the scan then runs all ranges in one launch
-    // and the lines of a document's ranges share fabric requests); the per-range arrays hold the extra lines only
-    void* shared = nullptr;
-    if (nr > 1) {
-      const size_t sb = (size_t)D.N * nr * 16 * D.l0_ppl + 256;
-      if (hipMalloc(&shared, sb) != hipSuccess) return fp_fail(FP_EHIP, "packed-code build failed (out of memory)");
-      ix->owned.push_back(shared);
-      ix->bytes += (int64_t)sb;
-      D.n_lines += D.N * nr;
-    }
-    for (int r = 0; r < nr; ++r) {
-      void* lines = nullptr; int32_t* poff = nullptr; int64_t nl = 0;
-      const int64_t lo = (int64_t)r << 17, hi = std::min<int64_t>(D.C, lo + (1ll << 17));
-      const int prc = fps_build_pcodes(D.ucodes, D.uoff, D.N, lo, hi, &lines, &poff, &nl, st, D.l0_ppl, D.C, shared, nr, r);
-      if (lines) { ix->owned.push_back(lines); ix->bytes += nl * 16 * D.l0_ppl; D.n_lines += nl; }
-      if (poff) { ix->owned.push_back(poff); ix->bytes += (D.N + 1) * 8; }
-      if (prc != 0) return fp_fail(FP_EHIP, "packed-code build failed (hip error " + std::to_string(prc) + ")");
-      D.pcodes_r[r] = static_cast<const uint4*>(lines); D.poff_r[r] = poff;
-    }
-    D.n_ranges = nr;
-    D.pcodes = nr > 1 ? static_cast<const uint4*>(shared) : D.pcodes_r[0]; D.poff = D.poff_r[0];
-  }
-  return FP_OK;
-}
-
-extern "C" int fp_index_create(const fp_index_desc* d, int device_id, fp_index** out) {
-  if (!d || !out) return fp_fail(FP_EINVAL, "null argument");
-  *out = nullptr;
-  if (int rc = check_shape(d->nbits, d->dim)) return rc;
-  if (d->n_centroids <= 0 || !d->centroids || !d->bucket_weights) return fp_fail(FP_EINVAL, "centroids / bucket_weights missing");
-  if (d->n_docs < 0 || (d->n_docs > 0 && (!d->doc_lengths || !d->doc_codes || !d->doc_residuals)))
-    return fp_fail(FP_EINVAL, "document arrays missing");
-  if (d->n_docs >= 0x7FFFFFFFll) return fp_fail(FP_EUNSUPPORTED, "more than 2^31-1 documents per index shard");
-  HIPCHK(fp_set_device(device_id));
-  fp_index* ix = new fp_index();
-  ix->device = device_id;
-  auto bail = [&](int rc) {
-    fp_index_destroy(ix);
-    return rc;
-  };
-  StreamGuard sg;
-  hipStream_t& st = sg.st;
-  FpIndexDev& D = ix->d;
-  D.nbits = d->nbits; D.dim = d->dim; D.pr = d->dim * d->nbits / 8;
-  D.C = d->n_centroids; D.N = d->n_docs; D.pid_offset = d->pid_offset;
-  // doc offsets (tensor.rs:221-224)
-  ix->h_doc_off.assign((size_t)D.N + 1, 0);
-  int maxlen = 0;
-  for (int64_t i = 0; i < D.N; ++i) {
-    int64_t l = d->doc_lengths[i];
-    if (l < 0) return bail(fp_fail(FP_EINVAL, "negative document length"));
-    ix->h_doc_off[i + 1] = ix->h_doc_off[i] + l;
-    if (l > maxlen) maxlen = (int)l;
-  }
-  D.T = ix->h_doc_off[D.N];
-  D.max_doc_len = maxlen;
-  uint16_t* cent = nullptr; uint16_t* lut = nullptr; int64_t* doc_off = nullptr; int32_t* codes = nullptr; uint8_t* res = nullptr;
-  int64_t* ivf_off = nullptr; int32_t* ivf_pids = nullptr;
-#define ICHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return bail(fp_fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e_) + " at " #x)); } while (0)
-  ICHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  ICHK(dev_alloc(ix, &cent, (size_t)D.C * D.dim));
-  ICHK(copy_sync(cent, d->centroids, (size_t)D.C * D.dim * 2, hipMemcpyHostToDevice, st));
-  ix->cent_norm_max = max_row_norm_f16(d->centroids, D.C, D.dim);
-  std::vector<uint16_t> hlut;
-  build_lut_host(D.nbits, d->bucket_weights, hlut);
-  ICHK(dev_alloc(ix, &lut, hlut.size()));
-  ICHK(copy_sync(lut, hlut.data(), hlut.size() * 2, hipMemcpyHostToDevice, st));
-  ICHK(dev_alloc(ix, &doc_off, (size_t)D.N + 1));
-  ICHK(copy_sync(doc_off, ix->h_doc_off.data(), ((size_t)D.N + 1) * 8, hipMemcpyHostToDevice, st));
-  ICHK(dev_alloc(ix, &codes, (size_t)D.T));
-  if (int rc = upload_narrow(d->doc_codes, codes, D.T, st, D.C, "doc_codes (centroid ids)")) return bail(rc);
-  ICHK(dev_alloc(ix, &res, (size_t)D.T * D.pr));
-  if (D.T > 0) ICHK(copy_sync(res, d->doc_residuals, (size_t)D.T * D.pr, hipMemcpyHostToDevice, st));
-  D.centroids = cent; D.lut = lut; D.doc_off = doc_off; D.codes = codes; D.residuals = res;
-  if (int rc = finish_layout(ix, maxlen, st)) return bail(rc);
-  ix->has_ivf = d->ivf != nullptr && d->ivf_lengths != nullptr;
-  D.P = ix->has_ivf ? d->n_ivf_lists : 0;
-  {
-    std::vector<int64_t> hoff((size_t)D.P + 1, 0);
-    for (int64_t i = 0; i < D.P; ++i) {
-      if (d->ivf_lengths[i] < 0) return bail(fp_fail(FP_EINVAL, "negative ivf length"));
-      hoff[i + 1] = hoff[i] + d->ivf_lengths[i];
-    }
-    ICHK(dev_alloc(ix, &ivf_off, hoff.size()));
-    ICHK(copy_sync(ivf_off, hoff.data(), hoff.size() * 8, hipMemcpyHostToDevice, st));
-    const int64_t tot = hoff[D.P];
-    ICHK(dev_alloc(ix, &ivf_pids, (size_t)tot));
-    if (tot > 0) {
-      if (int rc = upload_narrow(d->ivf, ivf_pids, tot, st, std::max<int64_t>(D.N, 1), "ivf (document ids)")) return bail(rc);
-      // The reference gathers the probed lists and sorts + de-duplicates the ids per query (search.rs:538-541): any order inside a
-      // list, repeated ids included, gives the same candidates there.  S3's per-tile range cut needs strictly ascending lists --
-      // what create.rs / update.rs / delete.rs write (optimize_ivf).  Anything else is put in that order here, once.
-      uint32_t* flag = nullptr;
-      ICHK(hipMalloc((void**)&flag, 4));
-      uint32_t h_flag = 0;
-      hipError_t fe = hipMemsetAsync(flag, 0, 4, st);
-      if (fe == hipSuccess) {
-        fpk_ivf_check_sorted(ivf_off, ivf_pids, D.P, flag, st);
-        fe = hipMemcpyAsync(&h_flag, flag, 4, hipMemcpyDeviceToHost, st);
-      }
-      if (fe == hipSuccess) fe = hipStreamSynchronize(st);
-      (void)hipFree(flag);
-      ICHK(fe);
-      if (h_flag) {
-        std::vector<int64_t> fixed;
-        fixed.reserve((size_t)tot);
-        std::vector<int64_t> noff((size_t)D.P + 1, 0);
-        for (int64_t i = 0; i < D.P; ++i) {
-          const size_t b = fixed.size();
-          fixed.insert(fixed.end(), d->ivf + hoff[i], d->ivf + hoff[i + 1]);
-          std::sort(fixed.begin() + b, fixed.end());
-          fixed.erase(std::unique(fixed.begin() + b, fixed.end()), fixed.end());
-          noff[i + 1] = (int64_t)fixed.size();
-        }
-        ICHK(copy_sync(ivf_off, noff.data(), noff.size() * 8, hipMemcpyHostToDevice, st));
-        if (int rc = upload_narrow(fixed.data(), ivf_pids, (int64_t)fixed.size(), st)) return bail(rc);
-      }
-    }
-  }
-  ICHK(hipStreamSynchronize(st));
-#undef ICHK
-  D.ivf_off = ivf_off; D.ivf_pids = ivf_pids;
-  prepay_legacy_stream();
-  *out = ix;
-  return FP_OK;
-}
-
-extern "C" void fp_index_destroy(fp_index* ix) {
-  if (!ix) return;
-  (void)fp_set_device(ix->device);
-  for (Scratch* s : ix->pool) {
-    s->destroy();
-    delete s;
-  }
-  for (void* p : ix->owned) (void)hipFree(p);
-  delete ix;
-}
-
-extern "C" int64_t fp_index_num_docs(const fp_index* ix) { return ix ? ix->d.N : 0; }
-extern "C" int64_t fp_index_num_tokens(const fp_index* ix) { return ix ? ix->d.T : 0; }
-extern "C" int64_t fp_index_num_centroids(const fp_index* ix) { return ix ? ix->d.C : 0; }
-extern "C" int32_t fp_index_dim(const fp_index* ix) { return ix ? ix->d.dim : 0; }
-extern "C" int32_t fp_index_nbits(const fp_index* ix) { return ix ? ix->d.nbits : 0; }
-extern "C" int64_t fp_index_device_bytes(const fp_index* ix) { return ix ? ix->bytes : 0; }
-extern "C" int64_t fp_index_num_unique_codes(const fp_index* ix) { return ix ? ix->d.U : 0; }
-extern "C" int64_t fp_index_num_code_lines(const fp_index* ix) { return ix ? ix->d.n_lines * ix->d.l0_ppl / 8 : 0; }   // in 128-byte units
-extern "C" int64_t fp_index_num_hard_tokens(const fp_index* ix) { return ix ? ix->n_hard_tokens : 0; }
-extern "C" int32_t fp_index_tickets_ok(const fp_index* ix) { return ix && ix->tickets_ok ? 1 : 0; }
-
-// ------------------------------------------------------------------------------------------
-// synthetic device-resident corpora
-// ------------------------------------------------------------------------------------------
-extern "C" int fp_index_create_synthetic(const fp_synth_desc* d, int device_id, fp_index** out) {
-  if (!d || !out) return fp_fail(FP_EINVAL, "null argument");
-  *out = nullptr;
-  if (int rc = check_shape(d->nbits, d->dim)) return rc;
-  if (d->n_centroids <= 1 || (d->n_centroids & (d->n_centroids - 1))) return fp_fail(FP_EINVAL, "n_centroids must be a power of two");
-  if (d->doc_begin < 0 || d->doc_end < d->doc_begin || d->doc_end > d->n_docs_total) return fp_fail(FP_EINVAL, "bad document range");
-  if (d->doc_len < 1) return fp_fail(FP_EINVAL, "doc_len < 1");
-  HIPCHK(fp_set_device(device_id));
-  fp_index* ix = new fp_index();
-  ix->device = device_id;
-  ix->synthetic = true;
-  auto bail = [&](int rc) {
-    fp_index_destroy(ix);
-    return rc;
-  };
-  FpSynthParams p{};
-  p.nbits = d->nbits; p.dim = d->dim; p.pr = d->dim * d->nbits / 8; p.C = d->n_centroids;
-  p.lgC = 0;
-  while ((1ll << p.lgC) < p.C) ++p.lgC;
-  p.n_docs_total = d->n_docs_total; p.doc_begin = d->doc_begin; p.doc_end = d->doc_end;
-  p.doc_len = d->doc_len; p.variable_len = d->variable_len; p.seed = d->seed;
-  FpIndexDev& D = ix->d;
-  D.nbits = p.nbits; D.dim = p.dim; D.pr = p.pr; D.C = p.C; D.P = p.C; D.N = p.doc_end - p.doc_begin; D.pid_offset = p.doc_begin;
-  std::vector<int64_t> hoff((size_t)D.N + 2, 0);
-  int maxlen = 0;
-  D.T = fps_doc_offsets_host(p, hoff.data(), &maxlen);
-  const int64_t tok_base = hoff[(size_t)D.N + 1];
-  D.max_doc_len = maxlen;
-  ix->h_doc_off.assign(hoff.begin(), hoff.begin() + D.N + 1);
-#define ICHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return bail(fp_fail(FP_EHIP, std::string("HIP error: ") + hipGetErrorString(e_) + " at " #x)); } while (0)
-  uint16_t* cent = nullptr; uint16_t* lut = nullptr; int64_t* doc_off = nullptr; int32_t* codes = nullptr; uint8_t* res = nullptr;
-  int64_t* ivf_off = nullptr; int32_t* ivf_pids = nullptr;
-  StreamGuard sg;
-  hipStream_t& st = sg.st;
-  ICHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  ICHK(dev_alloc(ix, &cent, (size_t)D.C * D.dim));
-  ICHK(copy_sync(cent, d->centroids, (size_t)D.C * D.dim * 2, hipMemcpyHostToDevice, st));
-  ix->cent_norm_max = max_row_norm_f16(d->centroids, D.C, D.dim);
-  std::vector<uint16_t> hlut;
-  build_lut_host(D.nbits, d->bucket_weights, hlut);
-  ICHK(dev_alloc(ix, &lut, hlut.size()));
-  ICHK(copy_sync(lut, hlut.data(), hlut.size() * 2, hipMemcpyHostToDevice, st));
-  ICHK(dev_alloc(ix, &doc_off, (size_t)D.N + 1));
-  ICHK(copy_sync(doc_off, ix->h_doc_off.data(), ((size_t)D.N + 1) * 8, hipMemcpyHostToDevice, st));
-  ICHK(dev_alloc(ix, &codes, (size_t)D.T));
-  ICHK(dev_alloc(ix, &res, (size_t)D.T * D.pr));
-  fps_generate(p, doc_off, D.N, D.T, tok_base, codes, res, st);
-  ICHK(hipStreamSynchronize(st));
-  D.centroids = cent; D.lut = lut; D.doc_off = doc_off; D.codes = codes; D.residuals = res;
-  if (int rc = finish_layout(ix, maxlen, st)) return bail(rc);
-  ICHK(dev_alloc(ix, &ivf_off, (size_t)D.P + 1));
-  int64_t tot = 0;
-  int rc = fps_build_ivf(D.ucodes, D.uoff, D.N, D.U, D.P, &ivf_pids, &tot, ivf_off, st);
-  if (ivf_pids) { ix->owned.push_back(ivf_pids); ix->bytes += tot * 4; }
-  if (rc != 0) return bail(fp_fail(FP_EHIP, "IVF build failed (hip/hipcub error " + std::to_string(rc) + ")"));
-  ICHK(hipStreamSynchronize(st));
-#undef ICHK
-  ix->has_ivf = true;
-  D.ivf_off = ivf_off; D.ivf_pids = ivf_pids;
-  prepay_legacy_stream();
-  *out = ix;
-  return FP_OK;
-}
-
-// one stored residual row -> the reference's byte order (identity unless the index keeps k_maxsim6's unit order)
-static inline void row_to_reference_order(const fp_index* ix, const uint8_t* stored, uint8_t* out) {
-  const int pr = ix->d.pr;
-  if (!ix->d.resid_native) { memcpy(out, stored, (size_t)pr); return; }
-  const int nbits = ix->d.nbits, nu = ix->d.dim / 8;
-  for (int b = 0; b < pr; ++b) out[b] = stored[fp_resid_pos(b, nbits, nu, 1)];
-}
-
-extern "C" int64_t fp_index_read_doc(const fp_index* ix, int64_t doc, int64_t* codes, uint8_t* residuals, int64_t cap) {
-  if (!ix || doc < 0 || doc >= ix->d.N) return fp_fail(FP_EINVAL, "bad document id");
-  (void)fp_set_device(ix->device);
-  const int64_t off = ix->h_doc_off[doc], len = ix->h_doc_off[doc + 1] - off;
-  if (len > cap) return fp_fail(FP_EINVAL, "capacity too small");
-  const int pr = ix->d.pr;
-  std::vector<int32_t> tmp((size_t)len);
-  std::vector<uint8_t> rtmp((size_t)len * pr);
-  std::vector<uint16_t> perm((size_t)len);
-  if (len > 0) {
-    HIPCHK(copy_sync(tmp.data(), ix->d.codes + off, (size_t)len * 4, hipMemcpyDeviceToHost, util_stream(ix->device)));
-    HIPCHK(copy_sync(rtmp.data(), ix->d.residuals + off * pr, (size_t)len * pr, hipMemcpyDeviceToHost, util_stream(ix->device)));
-    if (ix->d.perm) HIPCHK(copy_sync(perm.data(), ix->d.perm + off, (size_t)len * 2, hipMemcpyDeviceToHost, util_stream(ix->device)));
-  }
-  for (int64_t i = 0; i < len; ++i) {  // stored position i holds original token perm[i]
-    const int64_t p = ix->d.perm ? perm[i] : i;
-    codes[p] = tmp[i];
-    row_to_reference_order(ix, rtmp.data() + i * pr, residuals + p * pr);
-  }
-  return len;
-}
-
-extern "C" int64_t fp_index_read_ivf(const fp_index* ix, int64_t cell, int64_t* pids, int64_t cap) {
-  if (!ix || !ix->has_ivf || cell < 0 || cell >= ix->d.P) return fp_fail(FP_EINVAL, "bad cell");
-  (void)fp_set_device(ix->device);
-  int64_t be[2];
-  HIPCHK(copy_sync(be, ix->d.ivf_off + cell, 16, hipMemcpyDeviceToHost, util_stream(ix->device)));
-  const int64_t len = be[1] - be[0];
-  if (len > cap) return fp_fail(FP_EINVAL, "capacity too small");
-  std::vector<int32_t> tmp((size_t)len);
-  if (len > 0) HIPCHK(copy_sync(tmp.data(), ix->d.ivf_pids + be[0], (size_t)len * 4, hipMemcpyDeviceToHost, util_stream(ix->device)));
-  for (int64_t i = 0; i < len; ++i) pids[i] = tmp[i];
-  return len;
-}
 
 // ------------------------------------------------------------------------------------------
 // search pipeline
@@ -1521,15 +1062,9 @@ static int search_impl(fp_index* ix, const uint16_t* queries, int32_t nq, int32_
     }
     return FP_OK;
   }
-  Scratch* s = acquire(ix);
+  Lease lease(ix, Lease::kAbandonCapture);
+  Scratch* s = lease.s;
   if (!s) return fp_fail(FP_EHIP, "could not create a HIP stream");
-  struct Rel {
-    fp_index* ix; Scratch* s;
-    ~Rel() {
-      if (s->capturing) abandon_capture(s);   // an error return in the middle of a capture: close it, or the stream stays unusable
-      release(ix, s);
-    }
-  } rel{ix, s};
   const bool graph_env = g_graph_replay.load(std::memory_order_relaxed) != 0;
   const int Qp = fp_padded_qlen(Q);
   // sub-batch so that the centroid-score table stays within a budget
@@ -1850,9 +1385,9 @@ extern "C" int fp_maxsim_columns(const fp_index* cix, const uint16_t* query, int
     if (d < 0 || d >= D.N) return fp_fail(FP_EINVAL, "document id out of range");
     loc[(size_t)i] = (int32_t)d;
   }
-  Scratch* s = acquire(ix);
+  Lease lease(ix);
+  Scratch* s = lease.s;
   if (!s) return fp_fail(FP_EHIP, "could not create a HIP stream");
-  struct Rel { fp_index* ix; Scratch* s; ~Rel() { release(ix, s); } } rel{ix, s};
   hipStream_t st = s->st;
   fp_search_params prm{0, 4, 1, 1};
   FpSearchShape sh = make_shape(1, Q, &prm);
@@ -1933,9 +1468,9 @@ extern "C" int fp_reconstruct_embeddings(const fp_index* cix, const int64_t* doc
   const int64_t rows = (int64_t)tok.size();
   if (rows > cap_rows) return fp_fail(FP_EINVAL, "output capacity too small");
   if (rows == 0) return FP_OK;
-  Scratch* s = acquire(ix);
+  Lease lease(ix);
+  Scratch* s = lease.s;
   if (!s) return fp_fail(FP_EHIP, "could not create a HIP stream");
-  struct Rel { fp_index* ix; Scratch* s; ~Rel() { release(ix, s); } } rel{ix, s};
   HIPCHK(s->tok_idx.ensure((size_t)rows * 8));
   HIPCHK(s->recon.ensure((size_t)rows * ix->d.dim * 4));
   HIPCHK(hipMemcpyAsync(s->tok_idx.p, tok.data(), (size_t)rows * 8, hipMemcpyHostToDevice, s->st));
@@ -1979,9 +1514,9 @@ extern "C" int fp_token_scores(const fp_index* cix, const uint16_t* queries, int
   }
   if (!out || h == 0 || off == 0) return FP_OK;   // sizing call, or nothing to compute
   if (off > out_capacity) return fp_fail(FP_EINVAL, "output capacity too small");
-  Scratch* s = acquire(ix);
+  Lease lease(ix);
+  Scratch* s = lease.s;
   if (!s) return fp_fail(FP_EHIP, "could not create a HIP stream");
-  struct Rel { fp_index* ix; Scratch* s; ~Rel() { release(ix, s); } } rel{ix, s};
   const size_t qbytes = (size_t)nq * Q * dim * 2;
   HIPCHK(s->qin.ensure(qbytes));
   HIPCHK(s->tok_idx.ensure((size_t)h * 8 + tiles.size() * 4 + 64));   // hit_query | hit_pid (i32 each) | tiles (3 x i32 each)
@@ -2426,9 +1961,9 @@ extern "C" int fp_shard_search(const fp_index* cix, fp_comm* comm, const uint16_
   HIPCHK(fp_set_device(ix->device));
   for (int i = 0; i < nq; ++i) out_counts[i] = 0;
   if (p->top_k == 0) return FP_OK;
-  Scratch* s = acquire(ix);
+  Lease lease(ix, Lease::kSyncFirst);
+  Scratch* s = lease.s;
   if (!s) return fp_fail(FP_EHIP, "could not create a HIP stream");
-  struct Rel { fp_index* ix; Scratch* s; ~Rel() { (void)hipStreamSynchronize(s->st); release(ix, s); } } rel{ix, s};
   // Sub-batches against a FIXED budget of the centroid-score table (every rank must split the batch identically, so the budget
   // may not depend on a rank's free memory as fp_search's does): 16 GiB, FP_SHARD_S_BUDGET_KB for tests
   static const int64_t budget = [] { const double kb = fp_test_opt("shard_s_budget_kb", 0); return kb > 0 ? (int64_t)kb * 1024 : (16ll << 30); }();
@@ -2460,72 +1995,5 @@ extern "C" int fp_selftest_arith(int device_id, uint64_t* out_mismatches /*[16]*
   hipError_t e = copy_sync(out_mismatches, d, 128, hipMemcpyDeviceToHost, us);
   (void)hipFree(d);
   if (e != hipSuccess) return fp_fail(FP_EHIP, hipGetErrorString(e));
-  return FP_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// export the index arrays back to the host in the reference's construct_index layout
-// ------------------------------------------------------------------------------------------
-extern "C" int64_t fp_index_ivf_total(const fp_index* ix) {
-  if (!ix || !ix->has_ivf) return 0;
-  (void)fp_set_device(ix->device);
-  int64_t tot = 0;
-  if (copy_sync(&tot, ix->d.ivf_off + ix->d.P, 8, hipMemcpyDeviceToHost, util_stream(ix->device)) != hipSuccess) return fp_fail(FP_EHIP, "memcpy");
-  return tot;
-}
-
-extern "C" int fp_index_export(const fp_index* ix, int64_t* doc_codes, uint8_t* doc_residuals, int64_t* doc_lengths, int64_t* ivf,
-                               int32_t* ivf_lengths) {
-  if (!ix) return fp_fail(FP_EINVAL, "null argument");
-  HIPCHK(fp_set_device(ix->device));
-  const FpIndexDev& D = ix->d;
-  if (doc_lengths)
-    for (int64_t i = 0; i < D.N; ++i) doc_lengths[i] = ix->h_doc_off[i + 1] - ix->h_doc_off[i];
-  const int64_t chunk = 64ll << 20;
-  std::vector<int32_t> tmp;
-  std::vector<uint16_t> hperm;
-  if (D.perm && D.T > 0 && (doc_codes || doc_residuals)) {
-    hperm.resize((size_t)D.T);
-    HIPCHK(copy_sync(hperm.data(), D.perm, (size_t)D.T * 2, hipMemcpyDeviceToHost, util_stream(ix->device)));
-  }
-  // stored token i of document d is original token perm[i]: write it back to its original slot
-  auto orig_row = [&](int64_t doc, int64_t i) { return hperm.empty() ? i : ix->h_doc_off[doc] + hperm[i]; };
-  if (doc_codes) {
-    tmp.resize((size_t)std::max<int64_t>(D.T, 1));
-    if (D.T > 0) HIPCHK(copy_sync(tmp.data(), D.codes, (size_t)D.T * 4, hipMemcpyDeviceToHost, util_stream(ix->device)));
-    for (int64_t d0 = 0; d0 < D.N; ++d0)
-      for (int64_t i = ix->h_doc_off[d0]; i < ix->h_doc_off[d0 + 1]; ++i) doc_codes[orig_row(d0, i)] = tmp[i];
-  }
-  if (doc_residuals && D.T > 0) {
-    if (hperm.empty() && !D.resid_native) {
-      HIPCHK(copy_sync(doc_residuals, D.residuals, (size_t)D.T * D.pr, hipMemcpyDeviceToHost, util_stream(ix->device)));
-    } else {
-      std::vector<uint8_t> rt((size_t)std::min<int64_t>(chunk, D.T) * D.pr);
-      int64_t d0 = 0;
-      for (int64_t s0 = 0; s0 < D.T; s0 += chunk) {
-        const int64_t m = std::min(chunk, D.T - s0);
-        HIPCHK(copy_sync(rt.data(), D.residuals + s0 * D.pr, (size_t)m * D.pr, hipMemcpyDeviceToHost, util_stream(ix->device)));
-        for (int64_t i = s0; i < s0 + m; ++i) {
-          while (ix->h_doc_off[d0 + 1] <= i) ++d0;
-          row_to_reference_order(ix, rt.data() + (i - s0) * D.pr, doc_residuals + orig_row(d0, i) * D.pr);
-        }
-      }
-    }
-  }
-  if (ix->has_ivf && (ivf || ivf_lengths)) {
-    std::vector<int64_t> off((size_t)D.P + 1);
-    HIPCHK(copy_sync(off.data(), D.ivf_off, off.size() * 8, hipMemcpyDeviceToHost, util_stream(ix->device)));
-    if (ivf_lengths)
-      for (int64_t i = 0; i < D.P; ++i) ivf_lengths[i] = (int32_t)(off[i + 1] - off[i]);
-    if (ivf) {
-      const int64_t tot = off[D.P];
-      tmp.resize((size_t)std::min<int64_t>(chunk, std::max<int64_t>(tot, 1)));
-      for (int64_t s = 0; s < tot; s += chunk) {
-        const int64_t m = std::min(chunk, tot - s);
-        HIPCHK(copy_sync(tmp.data(), D.ivf_pids + s, (size_t)m * 4, hipMemcpyDeviceToHost, util_stream(ix->device)));
-        for (int64_t i = 0; i < m; ++i) ivf[s + i] = tmp[i];
-      }
-    }
-  }
   return FP_OK;
 }

@@ -7,7 +7,7 @@ do not cover) and by tests/test_rounding_fixtures_cpu.py.
                  the unfused chain are the same numbers)
   exact_dot      the same sum without any rounding, as an integer multiple of 2^-48
   wcol           S1's absolute window term of a query row, w0 * dim_scale * cent_norm_max * |q_n|_2 as k_pack_queries computes it
-                 (fp_kernels.hip) from the host's factor (fp_engine.cpp run_front, max_row_norm_f16)
+                 (fp_kernels.hip) from the host's factor (fp_engine.cpp run_front; max_row_norm_f16 of fp_index.cpp)
   s1_flagged     s1_certify's rule (fp_kernels.hip): u = fma(|x|, kappa, w); flagged when h(x + u) and h(x - u) differ in their bits
   maxsim_flagged the MaxSim column rule (fp_maxsim.hip, k_maxsim5 / k_maxsim6 epilogue): the fp32 column maximum lies within
                  eps_rel * |q_col|_2 of an fp16 rounding boundary
