@@ -1,6 +1,6 @@
-// The stand-alone index-build operators of the C ABI (include/fastplaid.h): fp_compress, fp_assign_l2, fp_kmeans and
-// fp_centroid_outliers, with their *_last_* queries.  Host code only: the kernels are behind the fpk_* launchers of fp_internal.h
-// (fp_index_ops.hip, fp_kmeans.hip, fp_outliers.hip).  Every operator follows one plan -- validate, select the device, a private
+// The stand-alone index-build operators of the C ABI (include/fastplaid.h): fp_compress, fp_assign_l2, fp_kmeans,
+// fp_centroid_outliers and fp_residual_stats, with their *_last_* queries.  Host code only: the kernels are behind the fpk_* launchers of fp_internal.h
+// (fp_index_ops.hip, fp_kmeans.hip, fp_outliers.hip, fp_codec_stats.hip).  Every operator follows one plan -- validate, select the device, a private
 // stream, a handful of device buffers, upload, chunks of at most 2^20 rows, download -- and BuildCall owns what that plan acquires.
 #include "../../include/fastplaid.h"
 
@@ -432,4 +432,73 @@ extern "C" int fp_centroid_outliers(int device_id, const uint16_t* centroids, in
   }
   *out_count = total;
   return g_co.publish(co, 1);
+}
+
+// Residual statistics for codec training (fastplaid.h fp_residual_stats): fp_compress's plan with the packing replaced by the
+// residual kernels of fp_codec_stats.hip.  The histogram and the per-dim sums stay on the device across the chunks and come back
+// once; codes and norms come back per chunk.
+extern "C" int fp_residual_stats(int device_id, const uint16_t* centroids, int64_t C, int32_t dim, const uint16_t* emb, int64_t T,
+                                 int64_t* out_codes, int64_t* out_hist, int64_t* out_abs_sum, float* out_norms) {
+  if (!centroids || !out_hist || !out_abs_sum || C < 1 || T < 0 || (T > 0 && !emb)) return fp_fail(FP_EINVAL, "bad argument");
+  if (!assign_dim_accepted(dim)) return fp_fail(FP_EUNSUPPORTED, "fp_residual_stats: dim must be in [1, 256] or a multiple of 8 up to 1024");
+  if (C >= 0x7FFFFFFFll) return fp_fail(FP_EUNSUPPORTED, "too many centroids");
+  BuildCall bc("fp_residual_stats", false);
+  if (int rc = bc.open(device_id)) return rc;
+  memset(out_hist, 0, 65536 * sizeof(int64_t));
+  memset(out_abs_sum, 0, (size_t)dim * sizeof(int64_t));
+  if (T == 0) return FP_OK;
+  const int64_t CHUNK = 1ll << 20;   // tokens per pass: at most 2^30 residuals, the bound of one fpk_hist16 launch
+  const int64_t cap = std::min<int64_t>(T, CHUNK);
+  Dev<uint16_t> d_cent(bc, (size_t)C * dim * 2);
+  Dev<uint16_t> d_emb(bc, (size_t)cap * dim * 2), d_res(bc, (size_t)cap * dim * 2);
+  Dev<int32_t> d_c32(bc, (size_t)cap * 4);
+  Dev<int64_t> d_c64(bc, out_codes ? (size_t)cap * 8 : 0);
+  Dev<float> d_norm(bc, out_norms ? (size_t)cap * 4 : 0);
+  Dev<int64_t> d_hist(bc, 65536 * 8), d_abs(bc, (size_t)dim * 8);
+  Dev<void> d_work(bc, fpk_compress_work_bytes(cap));
+  Dev<uint32_t> stat(bc, 64);   // [0] max |x| bits of the centroids, [1] of the embeddings so far
+  BCHK(hipStreamCreateWithFlags(&bc.st, hipStreamNonBlocking));
+  BCHK(bc.hip_malloc_all());
+  hipStream_t st = bc.st;
+  BCHK(hipMemsetAsync(stat, 0, 64, st));
+  BCHK(hipMemsetAsync(d_hist, 0, 65536 * 8, st));
+  BCHK(hipMemsetAsync(d_abs, 0, (size_t)dim * 8, st));
+  BCHK(hipMemcpyAsync(d_cent, centroids, (size_t)C * dim * 2, hipMemcpyHostToDevice, st));
+  fpk_km_scan_data(d_cent, C * dim, stat, st);
+  uint32_t h_max[2] = {0, 0};
+  BCHK(hipMemcpyAsync(h_max, stat, 4, hipMemcpyDeviceToHost, st));
+  BCHK(hipStreamSynchronize(st));
+  BCHK(hipGetLastError());
+  if (holds_non_finite(h_max[0])) return fp_fail(FP_EINVAL, "fp_residual_stats: the centroids hold a value that is not finite");
+  // max |centroid element| bounds the MFMA summation error in the assignment: the value fp_compress takes on the host
+  const float cmaxabs = std::ldexp((float)fp_f16_fixed((uint16_t)h_max[0]), -24);
+  for (int64_t t0 = 0; t0 < T; t0 += CHUNK) {
+    const int64_t n = std::min<int64_t>(CHUNK, T - t0);
+    BCHK(hipMemcpyAsync(d_emb, emb + t0 * dim, (size_t)n * dim * 2, hipMemcpyHostToDevice, st));
+    fpk_km_scan_data(d_emb, n * dim, stat + 1, st);
+    BCHK(hipMemcpyAsync(h_max + 1, stat + 1, 4, hipMemcpyDeviceToHost, st));
+    BCHK(hipStreamSynchronize(st));
+    BCHK(hipGetLastError());
+    if (holds_non_finite(h_max[1])) return fp_fail(FP_EINVAL, "fp_residual_stats: the embeddings hold a value that is not finite");
+    // exact sums in int64 units of 2^-24, |r| <= |x| + |c|: refuse what could leave 2^62 (the maximum so far only grows, so the
+    // last chunk decides with the maximum over all the data)
+    const unsigned __int128 reach = (unsigned __int128)fp_f16_fixed((uint16_t)h_max[0]) + (unsigned __int128)fp_f16_fixed((uint16_t)h_max[1]);
+    if ((unsigned __int128)T * reach >= ((unsigned __int128)1 << 62))
+      return fp_fail(FP_EUNSUPPORTED, "fp_residual_stats: n_tokens * (max|x| + max|c|) * 2^24 >= 2^62 (the exact fixed-point sums could overflow)");
+    if (int rc = fpk_assign_codes(d_emb, n, d_cent, C, dim, cmaxabs, d_c32, d_work, st))
+      return rc == -3 ? bc.hip_failed(hipGetLastError(), "fpk_assign_codes") : fp_fail(FP_EUNSUPPORTED, "fp_residual_stats: assignment chunk (" + std::to_string(rc) + ")");
+    fpk_residual_tile(d_emb, n, d_cent, C, dim, d_c32, d_res, d_abs, d_norm, d_c64, st);
+    if (int rc = fpk_hist16(d_res, n * dim, d_hist, st))
+      return rc == -3 ? bc.hip_failed(hipGetLastError(), "fpk_hist16") : fp_fail(FP_EUNSUPPORTED, "fp_residual_stats: histogram chunk (" + std::to_string(rc) + ")");
+    if (out_codes) BCHK(hipMemcpyAsync(out_codes + t0, d_c64, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    if (out_norms) BCHK(hipMemcpyAsync(out_norms + t0, d_norm, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    BCHK(hipStreamSynchronize(st));
+    BCHK(hipGetLastError());
+  }
+  BCHK(hipMemcpyAsync(out_hist, d_hist, 65536 * 8, hipMemcpyDeviceToHost, st));
+  BCHK(hipMemcpyAsync(out_abs_sum, d_abs, (size_t)dim * 8, hipMemcpyDeviceToHost, st));
+  BCHK(hipStreamSynchronize(st));
+  BCHK(hipGetLastError());
+  if (out_hist[0x7C00] != 0 || out_hist[0xFC00] != 0) return fp_fail(FP_EINVAL, "fp_residual_stats: a residual overflows fp16");
+  return FP_OK;
 }

@@ -1,5 +1,5 @@
 // Device-side helpers shared by the HIP translation units (fp_kernels.hip, fp_index_ops.hip, fp_token_scores.hip, fp_maxsim.hip,
-// fp_synth.hip, fp_kmeans.hip, fp_outliers.hip).  The host files (fp_engine.cpp, fp_build.cpp) do not include it.  gfx950 only.
+// fp_synth.hip, fp_kmeans.hip, fp_outliers.hip, fp_codec_stats.hip).  The host files (fp_engine.cpp, fp_build.cpp) do not include it.  gfx950 only.
 #pragma once
 #include <atomic>
 #include <hip/hip_runtime.h>

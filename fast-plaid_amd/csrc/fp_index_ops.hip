@@ -746,6 +746,14 @@ static int assign_codes(const uint16_t* emb, int64_t T, const uint16_t* cent, in
   return 0;
 }
 
+// the assignment half of fpk_compress alone (fp_residual_stats): the same codes, nothing packed
+int fpk_assign_codes(const uint16_t* emb, int64_t T, const uint16_t* cent, int64_t C, int D, float cmaxabs, int32_t* codes32, void* work,
+                     hipStream_t st) {
+  int64_t how[4] = {0, 0, 0, 0};
+  if (T <= 0) return 0;
+  return assign_codes(emb, T, cent, C, D, cmaxabs, codes32, work, st, how);
+}
+
 int fpk_compress(const uint16_t* emb, int64_t T, const uint16_t* cent, int64_t C, int D, int nbits, const uint16_t* cutoffs, float cmaxabs,
                  int32_t* codes32, int64_t* codes64, uint8_t* out, void* work, hipStream_t st, int64_t* how, hipEvent_t* ev) {
   int64_t how_[4] = {0, 0, 0, 0};

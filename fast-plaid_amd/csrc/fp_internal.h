@@ -1,4 +1,4 @@
-// Internal declarations shared by the HIP kernels (fp_kernels.hip, fp_index_ops.hip, fp_token_scores.hip, fp_kmeans.hip, fp_outliers.hip, fp_maxsim.hip, fp_synth.hip) and the
+// Internal declarations shared by the HIP kernels (fp_kernels.hip, fp_index_ops.hip, fp_token_scores.hip, fp_kmeans.hip, fp_outliers.hip, fp_codec_stats.hip, fp_maxsim.hip, fp_synth.hip) and the
 // host files (fp_engine.cpp: the search engine; fp_build.cpp: the stand-alone index-build operators).  Not part of the C ABI (see
 // include/fastplaid.h).
 #pragma once
@@ -429,6 +429,9 @@ void fpk_ivf_check_sorted(const int64_t* off, const int32_t* pids, int64_t P, ui
 size_t fpk_compress_work_bytes(int64_t T);
 int fpk_compress(const uint16_t* emb, int64_t T, const uint16_t* cent, int64_t C, int D, int nbits, const uint16_t* cutoffs, float cmaxabs,
                  int32_t* codes32, int64_t* codes64, uint8_t* out, void* work, hipStream_t st, int64_t* how = nullptr, hipEvent_t* ev = nullptr);
+// the assignment half of fpk_compress alone: codes32 [T] as fpk_compress computes them (same arguments, same return values)
+int fpk_assign_codes(const uint16_t* emb, int64_t T, const uint16_t* cent, int64_t C, int D, float cmaxabs, int32_t* codes32, void* work,
+                     hipStream_t st);
 // k-means assignment step: argmax_c (dot - half_sqnorm[c]) in fp32, ties -> lowest index
 int fpk_assign_l2(const uint16_t* emb, int64_t T, const uint16_t* cent, const float* half_sqnorm, int64_t C, int D, int32_t* codes32,
                   int64_t* codes64, hipStream_t st);
@@ -467,6 +470,14 @@ size_t fpk_outliers_tiles(int64_t T);
 void fpk_outliers_chunk(const uint16_t* emb, int64_t T, int64_t row0, const uint16_t* cent, int64_t C, int D, const float* half_sqnorm,
                         const int32_t* labels, float thr, float* sqdist, int64_t* nearest, uint8_t* flag, int32_t* tilecnt, int32_t* tileoff,
                         int32_t* count, int64_t* rows, hipStream_t st);
+// ---- fp_codec_stats.hip: fp_residual_stats (fp_build.cpp, include/fastplaid.h) behind the assignment -----------
+// one chunk with its codes: res [T][D] = h(emb[t][d] - cent[codes[t]][d]) (fp16 bits), abs_sum [D] += sum_t |res| in units of 2^-24
+// (int64, not zeroed here), norms [T] (nullable) = sqrt of the ascending-d fp32 chain of res^2, codes64 [T] (nullable) = the codes
+// widened.  A code outside [0, C) is read as 0.  D in [1, 1024]; a D that is not a multiple of 8 takes scalar loads
+void fpk_residual_tile(const uint16_t* emb, int64_t T, const uint16_t* cent, int64_t C, int D, const int32_t* codes, uint16_t* res,
+                       int64_t* abs_sum, float* norms, int64_t* codes64, hipStream_t st);
+// hist [65536] += the counts of the n <= 2^30 fp16 bit patterns of vals (16-byte aligned; int64, not zeroed here).  -2: n too large, -3: HIP error
+int fpk_hist16(const uint16_t* vals, int64_t n, int64_t* hist, hipStream_t st);
 // [q_len, doc_len] fp16 similarity matrices of (query, doc) hits; -1 when q_len * dim does not fit LDS
 int fpk_token_scores(const FpIndexDev& ix, const uint16_t* queries, int Q, const int32_t* hit_query, const int32_t* hit_pid, int64_t n_hits,
                      const int64_t* out_off, uint16_t* out, hipStream_t st);

@@ -55,8 +55,10 @@ def _rebuild_ivf(index_path: str, n_chunks: int, n_partitions: int):
     return int(codes.shape[0]), int(lens.shape[0])
 
 
-def update_index(index_path: str, documents_embeddings, device: str = "cuda:0", update_threshold: bool = False) -> None:
-    """update.rs:30-473."""
+def update_index(index_path: str, documents_embeddings, device: str = "cuda:0", update_threshold: bool = False,
+                 native_codec: bool = False) -> None:
+    """update.rs:30-473.  native_codec: with update_threshold, the residual norms come from the device (create.residual_stats)
+    instead of the host's (emb - cent[codes]) and its row sums."""
     meta_path = os.path.join(index_path, "metadata.json")
     meta = _read_json(meta_path)
     n_chunks = int(meta["num_chunks"])
@@ -87,7 +89,9 @@ def update_index(index_path: str, documents_embeddings, device: str = "cuda:0", 
         emb = np.concatenate(part)
         codes, packed = _create.compress(cent, cut, emb, nbits, device)
         lens = [int(d.shape[0]) for d in part]
-        if update_threshold:
+        if update_threshold and native_codec:
+            norms.append(_create.residual_stats(cent, emb, device)["norms"])
+        elif update_threshold:
             res = (emb - cent[codes]).astype(np.float32)
             norms.append(np.sqrt((res * res).sum(axis=1, dtype=np.float32)))
         g = start + i

@@ -186,13 +186,17 @@ class FastPlaid:
 
     def create(self, documents_embeddings, kmeans_niters: int = 4, max_points_per_centroid: int = 256, nbits: int = 4,
                n_samples_kmeans: int | None = None, seed: int = 42, use_triton_kmeans: bool | None = None, metadata=None,
-               compress_only: bool = False, centroids=None, *, start_from_scratch: int | None = None, batch_size: int = 25_000):
+               compress_only: bool = False, centroids=None, *, start_from_scratch: int | None = None, batch_size: int = 25_000,
+               native_codec: bool = False):
         """fast_plaid.py:398-560: k-means centroids (unless given), then the native part of the reference's create --
         codec training, compression, IVF, directory (rust/index/create.rs).  use_triton_kmeans=True (the reference's switch to its
         GPU k-means) selects the native trainer fp_kmeans; None / False keep the host loop around fp_assign_l2.
         start_from_scratch=<int> keeps the raw embeddings of a corpus of at most that many documents in embeddings.npy
         (fast_plaid.py:575-582; the reference's default is 1000), so that update(buffer_size=...) can rebuild a small index instead
-        of appending to it; None (the default) writes nothing.  batch_size is accepted for the reference's signature."""
+        of appending to it; None (the default) writes nothing.  batch_size is accepted for the reference's signature.
+        native_codec=True trains the codec from residual statistics computed on the device (fp_residual_stats: an exact histogram
+        instead of a host sort of n * dim residuals); opt-in like use_triton_kmeans, because avg_residual and the cluster threshold
+        differ from the host path's in their last bits (codes, packed residuals and the IVF do not)."""
         del batch_size
         if metadata is not None:
             raise NotImplementedError("metadata filtering (fast_plaid.filtering) is outside the MI355X search hot path")
@@ -210,14 +214,15 @@ class FastPlaid:
                                       [_to_np16(d[0] if getattr(d, "ndim", 2) == 3 else d) for d in documents_embeddings])
         from .. import create as _create
         _create.create_index(self.index, documents_embeddings, centroids, nbits=nbits, device=self.devices[0], seed=seed,
-                             compress_only=compress_only)
+                             compress_only=compress_only, native_codec=native_codec)
         self._last_known_mtime = 0.0
         self._check_and_reload_index()
         return self
 
     def update(self, documents_embeddings, metadata=None, batch_size: int = 25_000, update_threshold_centroids: bool = False, *,
                buffer_size: int | None = None, start_from_scratch: int = 999, kmeans_niters: int = 4, max_points_per_centroid: int = 256,
-               n_samples_kmeans: int | None = None, seed: int = 42, use_triton_kmeans: bool | None = False, **kwargs):
+               n_samples_kmeans: int | None = None, seed: int = 42, use_triton_kmeans: bool | None = False, native_codec: bool = False,
+               **kwargs):
         """fast_plaid.py:640-713.  buffer_size=None (the default here): rust/index/update.rs alone -- the documents are appended with
         the index's existing codec, and update_threshold_centroids folds their residual norms into cluster_threshold.npy.
         buffer_size=<int> runs the reference's policy around that step (maintain.process_update, update.py:206-452; the reference's
@@ -225,7 +230,8 @@ class FastPlaid:
         is rebuilt; small updates are appended and remembered in buffer.npy; once buffer_size documents have gathered, the embeddings
         farther than the cluster threshold from every centroid (fp_centroid_outliers) are clustered into new centroids
         (use_triton_kmeans selects fp_kmeans, as in create) and the buffered documents are inserted again.  The policy owns
-        update_threshold_centroids, so giving both raises ValueError."""
+        update_threshold_centroids, so giving both raises ValueError.  native_codec=True takes the residual norms of a threshold
+        update from the device (fp_residual_stats) and hands the switch on to a rebuild through create."""
         del kwargs
         if metadata is not None:
             raise NotImplementedError("metadata filtering (fast_plaid.filtering) is outside the MI355X search hot path")
@@ -234,7 +240,8 @@ class FastPlaid:
             del batch_size
             if self.index is None or not os.path.exists(os.path.join(self.index, "metadata.json")):
                 raise FileNotFoundError("no index to update: create it first")
-            maintain.update_index(self.index, documents_embeddings, self.devices[0], update_threshold=update_threshold_centroids)
+            maintain.update_index(self.index, documents_embeddings, self.devices[0], update_threshold=update_threshold_centroids,
+                                  native_codec=native_codec)
             self._last_known_mtime = 0.0
             self._check_and_reload_index()
             return self
@@ -253,7 +260,10 @@ class FastPlaid:
 
         def update_fn(index_path, device, embeddings, batch_size, update_threshold_centroids):
             del batch_size
-            maintain.update_index(index_path, embeddings, device, update_threshold=update_threshold_centroids)
+            maintain.update_index(index_path, embeddings, device, update_threshold=update_threshold_centroids, native_codec=native_codec)
+
+        def create_fn(**kw):
+            return self.create(native_codec=native_codec, **kw)
 
         def format_fn(docs):   # fast_plaid.py:411-425 (+ the fp16 cast of :241, which every consumer here applies anyway)
             return [_to_np16(d[0] if getattr(d, "ndim", 2) == 3 else d) for d in docs]
@@ -262,7 +272,7 @@ class FastPlaid:
             index_path=self.index, devices=self.devices, indices_dict=self.indices, documents_embeddings=documents_embeddings,
             metadata=metadata, batch_size=batch_size, kmeans_niters=kmeans_niters, max_points_per_centroid=max_points_per_centroid,
             n_samples_kmeans=n_samples_kmeans, seed=seed, start_from_scratch=start_from_scratch, buffer_size=buffer_size,
-            use_triton_kmeans=use_triton_kmeans, create_fn=self.create, delete_fn=self.delete, compute_kmeans_fn=compute_kmeans_fn,
+            use_triton_kmeans=use_triton_kmeans, create_fn=create_fn, delete_fn=self.delete, compute_kmeans_fn=compute_kmeans_fn,
             format_embeddings_fn=format_fn, update_fn=update_fn, reload_fn=reload_fn)
         self._last_known_mtime = 0.0
         self._check_and_reload_index()

@@ -345,6 +345,27 @@ int fp_centroid_outliers(int device_id, const uint16_t* centroids_f16 /*[n_centr
  * check, assignment, distance + compaction, download.  Returns 1 when that call succeeded, else 0 (the figures are stale). */
 int fp_centroid_outliers_last_counts(int64_t* out, int cap);
 
+/* Residual statistics the codec is trained from (rust/index/create.rs:317-364, and the norms of update.rs:283-310), on the device.
+ * Stand-alone like fp_compress: host buffers in and out, the embeddings in chunks of at most 2^20 rows, the centroids uploaded once.
+ * A residual is an fp16 value: the histogram of its 65 536 bit patterns gives EVERY order statistic of the residuals exactly, so
+ * the host reads the bucket cutoffs and weights from a cumulative sum instead of sorting n_tokens * dim values.  Pinned:
+ *   code[t]        = what fp_compress returns for the same centroids and embeddings (the same assignment code)
+ *   r[t][d]        = h(x[t][d] - cent[code[t]][d]), one fp32 subtraction rounded once to fp16 (the packed fp16 subtract)
+ *   out_hist[b]    = #{ (t, d) : bits(r[t][d]) == b }, summed over all chunks: integers, independent of order
+ *   out_abs_sum[d] = sum_t |r[t][d]| as an exact int64 in units of 2^-24 (fp_kmeans step 4); partial sums meet only in 64-bit
+ *                    integer atomics.  The mean is the caller's: (float)(((double)out_abs_sum[d] * 2^-24) / n_tokens)
+ *   out_norms[t]   = sqrt(chain), chain = the ascending-d fp32 sum of r[t][d]^2 (every square is exact in fp32, so fused and unfused
+ *                    accumulation give the same bits), the square root correctly rounded
+ * out_codes and out_norms are optional.  n_tokens == 0 succeeds with a zero histogram and zero sums.  dim as fp_compress: 1 .. 256
+ * (a dim that is not a multiple of 8 reads its rows element by element), or a multiple of 8 up to 1024.
+ * Errors: FP_EINVAL for a null or negative argument, a centroid or embedding value that is not finite (checked on the device), a
+ * residual that overflows fp16 (a non-zero count in bin 0x7C00 or 0xFC00 after the last chunk); FP_EUNSUPPORTED for any other dim,
+ * n_centroids >= 2^31-1, or n_tokens * (max|x| + max|c|) * 2^24 >= 2^62 (the maxima are taken on the device; beyond it an int64 sum
+ * could overflow); FP_EHIP from the runtime.  Every refusal that needs no device happens before the device is touched. */
+int fp_residual_stats(int device_id, const uint16_t* centroids_f16 /*[n_centroids, dim]*/, int64_t n_centroids, int32_t dim,
+                      const uint16_t* embeddings_f16 /*[n_tokens, dim]*/, int64_t n_tokens, int64_t* out_codes /*[n_tokens] or NULL*/,
+                      int64_t* out_hist /*[65536]*/, int64_t* out_abs_sum /*[dim], units of 2^-24*/, float* out_norms /*[n_tokens] or NULL*/);
+
 /* ---- `reconstruct_embeddings` (rust/utils/embeddings.rs:12-69) ----------------------- */
 /* Decompresses whole documents to fp32 rows. out: host [sum(len(doc)) , dim] f32 in the
  * order of doc_ids (ids may repeat); out_lengths [n]. `out_capacity_rows` guards the buffer: when it is too small the call fails
